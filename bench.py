@@ -1,6 +1,6 @@
 """bench.py — frames/s of DVIS++ R50 offline inference on synthetic 720p clips (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) re-executes itself as N ranks under torch.distributed.run
@@ -26,6 +26,7 @@ Also reported on the one JSON line:
                 per frame-layer) / its mean launch time (HIP events on the launch stream) vs 8 TB/s.
   roofline_tracker  the referring tracker's recurrence (its captured hipGraph replayed alone): the tracker's parameter bytes
                 x frames / replay time vs 8 TB/s — SURVEY.md §8(d)'s weight-streaming bound for the latency-bound chain.
+  dump_outputs  with --dump-outputs DIR: the arrays of the last timed step written to DIR (see dump_outputs()).
   cpu_baseline  the oracle's restatement of the reference pipeline (torch fp32 CPU ops, all host cores) on a bounded
                 sample of the same clip, in the metric's own unit, plus the oracle's C port of the MSDeformAttn kernel
                 (rank 0, N=1 only).
@@ -543,6 +544,64 @@ def other_configurations(model, clips, device, args):
     return out
 
 
+DUMP_BUDGET = 64 * 10 ** 6      # bytes written by --dump-outputs, all arrays together
+DUMP_SEED = 0
+
+
+def output_arrays(out):
+    """The arrays of one step's output dict, as a caller receives it -> {name: float32 / float64 numpy array}.  Tensors and
+    lists of same-shaped tensors keep their shape; integer tensors wider than 16 bits and python numbers become float64 (exact),
+    everything else float32; segments_infos becomes one row per segment, columns in sorted key order (category_id, id,
+    isthing); strings and events are left out."""
+    import numpy as np
+
+    def to_np(t):
+        t = t.detach().cpu()
+        wide = t.dtype in (torch.int32, torch.int64, torch.float64)
+        return t.to(torch.float64 if wide else torch.float32).numpy()
+
+    arrays = {}
+    for name in sorted(out):
+        v = out[name]
+        if torch.is_tensor(v):
+            arrays[name] = to_np(v)
+        elif isinstance(v, (list, tuple)):
+            if v and all(torch.is_tensor(x) for x in v):
+                arrays[name] = to_np(torch.stack(list(v)))
+            elif v and all(isinstance(x, dict) for x in v):
+                keys = sorted(v[0])
+                arrays[name] = np.array([[float(x[k]) for k in keys] for x in v], dtype=np.float64)
+            elif all(isinstance(x, (bool, int, float)) for x in v):
+                arrays[name] = np.array(v, dtype=np.float64).reshape(len(v))
+        elif isinstance(v, (bool, int, float)):
+            arrays[name] = np.array([v], dtype=np.float64)
+    return arrays
+
+
+def dump_outputs(out, path, budget=DUMP_BUDGET, seed=DUMP_SEED):
+    """--dump-outputs: write output_arrays(out) as path/<name>.npy, at most `budget` bytes in all.  Arrays up to budget / 64
+    bytes are written whole; the budget left is shared equally by the larger ones, each written as a fixed sample of its
+    flattened elements (sorted indices of numpy default_rng(seed).choice(numel, n, replace=False): the same sample for the same
+    shape, so two builds compare element for element).  -> {name: {"shape", "dtype", "sampled"}}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = output_arrays(out)
+    small = {k: a for k, a in arrays.items() if a.nbytes <= budget // 64}
+    large = {k: a for k, a in arrays.items() if a.nbytes > budget // 64}
+    left = budget - sum(a.nbytes for a in small.values()) - 256 * len(arrays)      # (256 B: room for each .npy header)
+    info = {}
+    for name, a in arrays.items():
+        sampled = None
+        if name in large:
+            n = min(a.size, max(0, left // len(large)) // a.itemsize)
+            if n < a.size:
+                idx = np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))
+                a, sampled = a.reshape(-1)[idx], int(n)
+        np.save(os.path.join(path, name + ".npy"), a)
+        info[name] = {"shape": list(arrays[name].shape), "dtype": str(a.dtype), "sampled": sampled}
+    return info
+
+
 BB_NAME = {"r50": "R50", "vitl": "ViT-Adapter-L", "vitb": "ViT-Adapter-B"}
 
 
@@ -594,6 +653,9 @@ def main():
                          "stream (all K clips complete inside the timed region); 0 = one forward() per clip, back to back")
     ap.add_argument("--rounds", type=int, default=0,
                     help="offline mode: spans handed to the tracker while the segmenter runs the next span (0 = default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; float32 / "
+                         "float64, at most 64 MB in all: larger outputs as a fixed, seeded sample, see dump_outputs)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))           # one rank per GPU under torch.distributed.run; rank 0 prints the line
@@ -727,6 +789,9 @@ def main():
         # 4 ranks 0.65 / 0.72 / 0.77 of linear at 1 / 2 / 4 clips per round, 8 ranks 0.47 / 0.56 / 0.61; 2 ranks 0.86 / 0.92 / 0.92
         model.tracker_batch = 4      # (final commit: 2 ranks 0.81 / 0.90 / 0.92, 4 ranks 0.61 / 0.71 / 0.77, 8 ranks 0.44 / 0.55 / 0.62)
     dt, outs, lat, timer, warm_clips = timed(owner_rounds=False if world > 1 else owner_default)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(outs[-1], args.dump_outputs)      # the headline pass's last step, before any other pass runs
     owner_line = None
     if world > 1 and streamed and owner_default:
         dt_o, outs_o, lat_o, _, warm_o = timed(owner_rounds=True)
@@ -984,6 +1049,8 @@ def main():
                                      "peak": round(L1_PATH_PEAK_GBS, 1), "unit": "GB/s",
                                      "frac": round(MSDA_GATHERED_BYTES_PER_FRAME_LAYER * nfr / sec / 1e9 / L1_PATH_PEAK_GBS, 4)}},
         }
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "step": args.steps - 1, "arrays": dumped}
         if dist_info is not None:
             res["dist"] = dist_info
         if conv_roof is not None:

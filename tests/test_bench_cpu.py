@@ -87,3 +87,33 @@ def test_committed_pmc_traffic_files_are_readable():
     t = bench.load_x3_traffic()
     for fam in ("conv1x1_x3_kernel", "x3_ffn_kernel"):
         assert fam in t and t[fam]["hbm_bytes_per_launch"] > 0 and "FETCH_SIZE" in t[fam]["source"]
+
+
+def test_dump_outputs_writes_a_step_within_the_budget(tmp_path):
+    """--dump-outputs: every array of a step's output dict as <name>.npy in float32 / float64; an output larger than the budget
+    is written as the same seeded sample of its elements on every run; small arrays and segments_infos are written whole."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(0)
+    panoptic = torch.randint(0, 7, (4, 72, 128), generator=g, dtype=torch.int32)
+    out = {"image_size": (72, 128), "pred_masks": panoptic, "pred_ids": [3, 1, 4], "num_candidates": 5, "task": "vps",
+           "segments_infos": [{"id": 1, "isthing": True, "category_id": 2}, {"id": 2, "isthing": False, "category_id": 9}],
+           "logits": torch.randn(3, 5, generator=g)}
+    budget = 64 * 1024
+    info = bench.dump_outputs(out, str(tmp_path / "a"), budget=budget)
+    bench.dump_outputs(out, str(tmp_path / "b"), budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["image_size.npy", "logits.npy", "num_candidates.npy", "pred_ids.npy", "pred_masks.npy", "segments_infos.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "segments_infos.npy"), [[2, 1, 1], [9, 2, 0]])
+    assert np.array_equal(np.load(tmp_path / "a" / "pred_ids.npy"), [3, 1, 4])
+    assert np.array_equal(np.load(tmp_path / "a" / "logits.npy"), out["logits"].numpy())
+    m = np.load(tmp_path / "a" / "pred_masks.npy")
+    n = info["pred_masks"]["sampled"]
+    assert info["pred_masks"]["shape"] == [4, 72, 128] and 0 < n == m.size < panoptic.numel()
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(panoptic.numel(), n, replace=False))
+    assert np.array_equal(m, panoptic.reshape(-1).numpy()[idx].astype(np.float64))

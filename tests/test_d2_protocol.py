@@ -6,8 +6,8 @@ The reference's launcher builds its model with detectron2's ``build_model``:
 calls ``build_pixel_decoder`` / ``build_transformer_decoder`` (mask_former_head.py:88-116 ->
 maskformer_transformer_decoder.py:16-27).  Here the same third-party stubs tests/golden/_ref_import.py uses stand in for
 detectron2's registries, ``d2.install()`` writes this build's classes into them, and the model is built from the
-REFERENCE'S OWN yaml (configs/dvis_Plus/VIPSeg/DVIS_Plus_Offline_R50.yaml with its _BASE_ chain — read directly when
-/root/reference exists, from the committed resolved copy otherwise) exactly the way detectron2 would.
+REFERENCE'S OWN yaml (configs/dvis_Plus/VIPSeg/DVIS_Plus_Offline_R50.yaml with its _BASE_ chain, as the committed resolved
+copy tests/golden/cfg_*.json that tests/golden/gen_cfg_fixtures.py writes) exactly the way detectron2 would.
 """
 import json
 import os
@@ -20,7 +20,6 @@ import torch
 from conftest import GOLDEN
 
 sys.path.insert(0, GOLDEN)
-REF_CFG = "/root/reference/DVIS_Plus/configs/dvis_Plus/VIPSeg"
 
 VIPSEG_THING_IDS = [2, 4, 8, 10, 41, 43, 44, 46, 47, 48, 49, 50, 51, 52, 54, 55, 56, 60, 61, 62, 63, 64, 65, 72, 74, 76, 77, 78,
                     79, 82, 83, 84, 85, 86, 87, 88, 89, 90, 91, 92, 95, 96, 97, 99, 100, 101, 102, 106, 107, 108, 109, 114,
@@ -28,18 +27,12 @@ VIPSEG_THING_IDS = [2, 4, 8, 10, 41, 43, 44, 46, 47, 48, 49, 50, 51, 52, 54, 55,
 
 
 def _cfg(name, rel):
+    """The defaults overlaid with the committed fixture `name`: the reference's configs/dvis_Plus/VIPSeg/`rel` with its _BASE_
+    chain resolved (what cfg.merge_from_file of that yaml overlays)."""
     from dvis_plus_amd.config import CfgNode, get_default_cfg
-    cfg = get_default_cfg()
-    fixture = CfgNode(json.load(open(os.path.join(GOLDEN, name + ".json"))))
-    path = os.path.join(REF_CFG, rel)
-    if os.path.exists(path):                                    # build container: the yaml itself
-        cfg.merge_from_file(path)
-        direct = get_default_cfg().merge(fixture)
-        assert json.dumps(cfg, sort_keys=True, default=str) == json.dumps(direct, sort_keys=True, default=str), \
-            "committed cfg fixture is stale w.r.t. the reference's yaml"
-    else:
-        cfg.merge(fixture)
-    return cfg
+    path = os.path.join(GOLDEN, name + ".json")
+    assert os.path.exists(path), f"{path}: resolved copy of {rel} missing (tests/golden/gen_cfg_fixtures.py writes it)"
+    return get_default_cfg().merge(CfgNode(json.load(open(path))))
 
 
 @pytest.fixture
