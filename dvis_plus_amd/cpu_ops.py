@@ -69,3 +69,47 @@ def attn_mask(mask_embed, mask_features, target_size):
                           align_corners=False)
     blocked = small.sigmoid().flatten(2) < 0.5
     return blocked.to(torch.uint8), (~blocked).sum(-1).to(torch.int32)
+
+
+# --- video metrics (csrc/video_metrics.hip): the same counts by torch.bincount -------------------------------------------------
+def pan_pair_hist(gt, pred, gt_table, num_pred):
+    """(T, Ng + 2, Np + 1) int64 pair counts and the number of predictions outside 0..Np (see dvis_pan_pair_hist)."""
+    T = gt.shape[0]
+    ng, np1 = gt_table.numel(), num_pred + 1
+    g, p = gt.reshape(T, -1).long(), pred.reshape(T, -1).long()
+    table = gt_table.long()
+    pos = torch.searchsorted(table, g).clamp_(max=max(ng - 1, 0))
+    found = table[pos] == g if ng else torch.zeros_like(g, dtype=torch.bool)
+    row = torch.where(g == 0, 0, torch.where(found, pos + 1, ng + 1))
+    ok = (p >= 0) & (p <= num_pred)
+    frame = torch.arange(T).view(T, 1).expand_as(g)
+    idx = (frame * (ng + 2) + row) * np1 + p
+    counts = torch.bincount(idx[ok], minlength=T * (ng + 2) * np1)
+    return counts.view(T, ng + 2, np1), int((~ok).sum())
+
+
+def sem_confusion(gt, pred, num_class):
+    """(num_class, num_class) int64 confusion of eval_miou_vspw.py:_generate_matrix and the count of `bad` pixels."""
+    g = gt.reshape(-1).long() & 255
+    g = (torch.where(g == 0, 255, g) - 1) & 255
+    p = pred.reshape(-1).long()
+    keep = g < num_class
+    b = num_class * g[keep] + p[keep]
+    ok = (p[keep] >= 0) & (b < num_class * num_class)
+    return torch.bincount(b[ok], minlength=num_class * num_class).view(num_class, num_class), int((~ok).sum())
+
+
+def video_consistency(gt, pred, ks):
+    """(gt_const, both_const), each (len(ks), T) int64: eval_vc_vspw.py:get_common's counts per window start i < T - k."""
+    T = gt.shape[0]
+    g, p = gt.reshape(T, -1), pred.reshape(T, -1)
+    gc = torch.zeros((len(ks), T), dtype=torch.int64)
+    bc = torch.zeros((len(ks), T), dtype=torch.int64)
+    same_g = g[1:] == g[:-1]                  # frame t + 1 equals frame t
+    same_p = p[1:] == p[:-1]
+    for j, k in enumerate(ks):
+        for i in range(T - k):
+            cg = same_g[i:i + k - 1].all(0)
+            gc[j, i] = cg.sum()
+            bc[j, i] = (cg & same_p[i:i + k - 1].all(0)).sum()
+    return gc, bc

@@ -2151,3 +2151,95 @@ def bias_act_(x, bias=None, res=None, relu=True):
                                         1 if relu else 0, native.stream_ptr(x.device))
     native.check(rc, "dvis_bias_act")
     return x
+
+
+# --- video metrics: integer counts over (T, H, W) id maps (csrc/video_metrics.hip) -----------------------------------------------
+# Dispatch by device: GPU tensors run the kernel (or raise), CPU tensors take the bincount formulations of cpu_ops.py.  Inputs may
+# be any integer dtype and layout; they are made contiguous int32 first (one copy when they are not already).
+def _i32(t, name):
+    if t.dtype.is_floating_point or t.dtype == torch.bool or t.is_complex():
+        raise RuntimeError(f"{name} must be an integer map, got {t.dtype}")
+    return t.to(torch.int32).contiguous()
+
+
+def _same_device(*ts):
+    devs = {t.device for t in ts}
+    if len(devs) != 1:
+        raise RuntimeError(f"video metrics: tensors on different devices {sorted(map(str, devs))}")
+    return ts[0].is_cuda
+
+
+def pan_pair_hist(gt, pred, gt_table, num_pred, check=True):
+    """Per-frame (GT segment, predicted segment) pixel counts of a clip (see dvis_pan_pair_hist).  gt (T, H, W): raw GT ids
+    (r + 256 g + 65536 b, 0 = VOID); pred (T, H, W): dense predicted ids 0..num_pred; gt_table: the video's GT ids, sorted,
+    non-zero.  Returns int64 (T, Ng + 2, num_pred + 1): row 0 VOID, 1 + i gt_table[i], Ng + 1 ids not in the table.
+    check: validate the table and raise when a prediction lies outside 0..num_pred (host syncs)."""
+    if gt.shape != pred.shape or gt.dim() != 3:
+        raise RuntimeError(f"pan_pair_hist: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} must be the same (T, H, W)")
+    table = gt_table.reshape(-1)
+    if check and table.numel() and bool((table[1:] <= table[:-1]).any() or (table <= 0).any()):
+        raise ValueError("pan_pair_hist: gt_table must be strictly increasing positive ids")
+    if not _same_device(gt, pred, table):
+        counts, bad = cpu_ops.pan_pair_hist(gt, pred, table, int(num_pred))
+    else:
+        T, H, W = gt.shape
+        g, p, tb = _i32(gt, "gt"), _i32(pred, "pred"), _i32(table, "gt_table")
+        counts = torch.empty((T, tb.numel() + 2, int(num_pred) + 1), dtype=torch.int64, device=g.device)
+        badt = torch.empty((1,), dtype=torch.int64, device=g.device)
+        with torch.cuda.device(g.device):
+            rc = native.lib().dvis_pan_pair_hist(native.dev_ptr(g, "gt"), native.dev_ptr(p, "pred"),
+                                                 native.dev_ptr(tb, "gt_table") if tb.numel() else None, tb.numel(),
+                                                 int(num_pred), T, H * W, native.dev_ptr(counts, "out"),
+                                                 native.dev_ptr(badt, "bad"), native.stream_ptr(g.device))
+        native.check(rc, "dvis_pan_pair_hist")
+        bad = int(badt.item()) if check else 0
+    if check and bad:
+        raise ValueError(f"pan_pair_hist: {bad} predicted pixels outside 0..{num_pred}")
+    return counts
+
+
+def sem_confusion(gt, pred, num_class, check=True):
+    """Class confusion (num_class, num_class) int64 of eval_miou_vspw.py:_generate_matrix over all pixels of gt / pred (same
+    shape): VSPW labels (0 -> 255, - 1 in uint8, rows >= num_class dropped).  check: raise when a pixel would fall outside the
+    matrix (negative prediction, or a bin past num_class^2, where the reference's reshape fails)."""
+    if gt.shape != pred.shape:
+        raise RuntimeError(f"sem_confusion: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} differ")
+    if not _same_device(gt, pred):
+        conf, bad = cpu_ops.sem_confusion(gt, pred, int(num_class))
+    else:
+        g, p = _i32(gt, "gt"), _i32(pred, "pred")
+        conf = torch.empty((int(num_class), int(num_class)), dtype=torch.int64, device=g.device)
+        badt = torch.empty((1,), dtype=torch.int64, device=g.device)
+        with torch.cuda.device(g.device):
+            rc = native.lib().dvis_sem_confusion(native.dev_ptr(g, "gt") if g.numel() else None,
+                                                 native.dev_ptr(p, "pred") if p.numel() else None, g.numel(), int(num_class),
+                                                 native.dev_ptr(conf, "out"), native.dev_ptr(badt, "bad"),
+                                                 native.stream_ptr(g.device))
+        native.check(rc, "dvis_sem_confusion")
+        bad = int(badt.item()) if check else 0
+    if check and bad:
+        raise ValueError(f"sem_confusion: {bad} pixels fall outside the {num_class} x {num_class} matrix")
+    return conf
+
+
+def video_consistency(gt, pred, ks=(8, 16)):
+    """eval_vc_vspw.py:get_common's counts for a (T, H, W) clip: (gt_const, both_const), each (len(ks), T) int64 — for window
+    length ks[j] and start i < T - k (the reference's range), the pixels whose GT is constant over [i, i + k) and those whose
+    prediction is constant there too.  Entries i >= T - k are zero."""
+    if gt.shape != pred.shape or gt.dim() != 3:
+        raise RuntimeError(f"video_consistency: gt {tuple(gt.shape)} and pred {tuple(pred.shape)} must be the same (T, H, W)")
+    ks = [int(k) for k in ks]
+    if not _same_device(gt, pred):
+        return cpu_ops.video_consistency(gt, pred, ks)
+    T, H, W = gt.shape
+    g, p = _i32(gt, "gt"), _i32(pred, "pred")
+    gc = torch.empty((len(ks), T), dtype=torch.int64, device=g.device)
+    bc = torch.empty((len(ks), T), dtype=torch.int64, device=g.device)
+    karr = (ctypes.c_int32 * len(ks))(*ks)
+    with torch.cuda.device(g.device):
+        rc = native.lib().dvis_video_consistency(native.dev_ptr(g, "gt") if g.numel() else None,
+                                                 native.dev_ptr(p, "pred") if p.numel() else None, T, H * W,
+                                                 ctypes.cast(karr, ctypes.c_void_p), len(ks), native.dev_ptr(gc, "gt_const"),
+                                                 native.dev_ptr(bc, "both_const"), native.stream_ptr(g.device))
+    native.check(rc, "dvis_video_consistency")
+    return gc, bc

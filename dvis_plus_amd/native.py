@@ -133,6 +133,9 @@ SIGNATURES = {
     "dvis_gemm_pick_config": (_i, [_i, _i, _i, _i]),
     "dvis_gemm_pick_config_nw": (_i, [_i, _i, _i, _i, _i]),
     "dvis_gemm_config_waves": (_i, [_i]),
+    "dvis_pan_pair_hist": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p, _p, _p]),
+    "dvis_sem_confusion": (_i, [_p, _p, _i64, _i, _p, _p, _p]),
+    "dvis_video_consistency": (_i, [_p, _p, _i, _i64, _p, _i, _p, _p, _p]),
 }
 
 _lib = None

@@ -57,6 +57,10 @@
  *   dvis_conv1x1_x3          <- the compute-bound 1x1 convolutions of the R50 bottlenecks (as dvis_conv1x1_mfma) in that arithmetic
  *   dvis_bneck_x3            <- the res2 bottlenecks (detectron2 BottleneckBlock.forward: conv2 -> conv3 + shortcut -> the next block's
  *                               conv1) as one kernel per block, 64-channel maps as pre-split operand images
+ *   dvis_pan_pair_hist / dvis_sem_confusion / dvis_video_consistency
+ *                            <- the pixel passes of the VPS / VSS scoring scripts, utils/eval_vpq_vspw.py:77-216,
+ *                               utils/segmentation_and_tracking_quality.py:131-221, utils/eval_miou_vspw.py:43-56,
+ *                               utils/eval_vc_vspw.py:8-23 (csrc/video_metrics.hip)
  */
 #ifndef DVIS_HIP_H
 #define DVIS_HIP_H
@@ -694,6 +698,30 @@ int dvis_x3_ffn_pack(const float *W1, int64_t ldw1, const float *W2, int64_t ldw
 int dvis_x3_ffn_ln(const float *x, int64_t ldx, int64_t M, int K, int H, int N, const void *packed, int xexp, int w1exp,
                    int hexp, int w2exp, const float *b1, const float *b2, const float *gamma, const float *beta, float eps,
                    const float *pos, int64_t pos_rows, float *out, float *out2, int64_t ldo, void *stream);
+
+/*
+ * Video metrics (csrc/video_metrics.hip): integer counts over (T, H, W) int32 id maps, u64 atomics only — run-to-run identical.
+ * Outputs are zeroed inside.  `bad` (one int64): pixels whose prediction lies outside the declared range (not counted elsewhere).
+ *
+ * dvis_pan_pair_hist: per-frame (GT segment, predicted segment) pixel counts, out (T, Ng + 2, Np + 1) int64.  GT rows: 0 = VOID
+ *   (id 0), 1 + i = gt_table[i] (the video's GT ids, sorted ascending, non-zero, Ng <= 16384), Ng + 1 = an id that the table does
+ *   not list (the reference skips those segments, utils/eval_vpq_vspw.py:167-170, but their pixels still count in the prediction
+ *   areas); prediction columns 0..Np.  Replaces the np.unique of uint64 `gt * 2^24 + pred` tubes per window start and length
+ *   (utils/eval_vpq_vspw.py:142-148) and the per-frame pair counts of utils/segmentation_and_tracking_quality.py:131-221.
+ *   H * W < 2^31.
+ */
+int dvis_pan_pair_hist(const int32_t *gt, const int32_t *pred, const int32_t *gt_table, int Ng, int Np, int T, int64_t HW,
+                       int64_t *out, int64_t *bad, void *stream);
+/* dvis_sem_confusion: the class confusion of utils/eval_miou_vspw.py:_generate_matrix over n pixels, out (num_class, num_class) int64
+ *   (num_class <= 256): gt taken as uint8, 0 -> 255, then - 1 in uint8, rows >= num_class dropped; bin = num_class * gt + pred (a
+ *   prediction >= num_class lands in the next row, as in the reference's bincount); pred < 0 or a bin past the matrix -> bad. */
+int dvis_sem_confusion(const int32_t *gt, const int32_t *pred, int64_t n, int num_class, int64_t *out, int64_t *bad, void *stream);
+/* dvis_video_consistency: utils/eval_vc_vspw.py:get_common in one pass over the frames per pixel.  For each window length ks[j]
+ *   (HOST array, 1 <= nk <= 4) and start i in the reference's range(T - k) (i < T - k; the last valid window is not scored there):
+ *   gt_const[j][i] = pixels whose GT is constant over frames [i, i + k), both_const[j][i] = those whose prediction is constant
+ *   there too.  Outputs (nk, T) int64, entries i >= T - k zero.  2 * nk * T <= 16384. */
+int dvis_video_consistency(const int32_t *gt, const int32_t *pred, int T, int64_t HW, const int32_t *ks, int nk, int64_t *gt_const,
+                           int64_t *both_const, void *stream);
 
 #ifdef __cplusplus
 }
