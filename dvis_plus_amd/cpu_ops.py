@@ -113,3 +113,73 @@ def video_consistency(gt, pred, ks):
             gc[j, i] = cg.sum()
             bc[j, i] = (cg & same_p[i:i + k - 1].all(0)).sum()
     return gc, bc
+
+
+# --- VIS scoring (csrc/vis_metrics.hip): COCO RLE and track intersections by plain torch ops -----------------------------------
+def _run_index(run_off):
+    """(mask of each run, index of each run inside its mask) for runs laid out at run_off (N + 1)."""
+    n_runs = run_off[1:] - run_off[:-1]
+    mask = torch.repeat_interleave(torch.arange(n_runs.numel()), n_runs)
+    return mask, torch.arange(mask.numel()) - run_off[mask]
+
+
+def rle_encode(masks):
+    """(runs int32, run_off (N + 1) int64, area (N) int64) of (N, H, W) masks: COCO runs in column-major order, zeros first."""
+    N, H, W = masks.shape
+    m = (masks != 0).transpose(1, 2).reshape(N, H * W).to(torch.int8)
+    prev = torch.cat((torch.zeros((N, 1), dtype=torch.int8), m[:, :-1]), 1)
+    n, pos = torch.nonzero(m != prev, as_tuple=True)            # row-major: by mask, then position
+    moff = torch.zeros(N + 1, dtype=torch.int64)
+    moff[1:] = torch.bincount(n, minlength=N).cumsum(0)
+    run_off = moff + torch.arange(N + 1)
+    at = run_off[n] + torch.arange(n.numel()) - moff[n]          # run index that ends at boundary `pos`
+    ends = torch.empty(int(run_off[-1]), dtype=torch.int64)
+    starts = torch.empty_like(ends)
+    ends[at], starts[at + 1] = pos, pos
+    ends[run_off[1:] - 1] = H * W
+    starts[run_off[:-1]] = 0
+    return (ends - starts).to(torch.int32), run_off, m.sum(1, dtype=torch.int64)
+
+
+def rle_strings(runs, run_off):
+    """(chars uint8, str_off (N + 1) int64): cocoapi's rleToString of every mask, concatenated."""
+    cnt = runs.long()
+    mask, i = _run_index(run_off)
+    x = cnt.clone()
+    back = i > 2
+    x[back] -= cnt[torch.nonzero(back, as_tuple=True)[0] - 2]
+    active = torch.ones_like(x, dtype=torch.bool)
+    cols = []
+    for _ in range(8):                                           # a 33-bit signed delta takes at most 7 groups
+        c = x & 0x1f
+        x = x >> 5
+        more = torch.where((c & 0x10) != 0, x != -1, x != 0)
+        cols.append(torch.where(active, torch.where(more, c | 0x20, c) + 48, -1))
+        active &= more
+    assert not bool(active.any())
+    chars = torch.stack(cols, 1)
+    valid = chars >= 0
+    str_off = torch.zeros(run_off.numel(), dtype=torch.int64)
+    str_off[1:] = torch.zeros(run_off.numel() - 1, dtype=torch.int64).index_add_(0, mask, valid.sum(1)).cumsum(0)
+    return chars[valid].to(torch.uint8), str_off
+
+
+def rle_decode(runs, run_off, H, W):
+    """(N, H, W) uint8 0 / 1 masks from their runs (each mask's runs must sum to H * W)."""
+    N = run_off.numel() - 1
+    _, i = _run_index(run_off)
+    flat = torch.repeat_interleave((i & 1).to(torch.uint8), runs.long())
+    if flat.numel() != N * H * W:
+        raise ValueError(f"rle_decode: the runs cover {flat.numel()} pixels, not {N} x {H} x {W}")
+    return flat.view(N, W, H).transpose(1, 2).contiguous()
+
+
+def track_intersections(pred, gt):
+    """(P, G) int64: sum over frames of |pred[p, t] & gt[g, t]| for pred (P, T, ...) and gt (G, T, ...) masks."""
+    P, G, T = pred.shape[0], gt.shape[0], pred.shape[1]
+    out = torch.zeros((P, G), dtype=torch.float64)
+    for t in range(T):                                           # float64 sums of 0 / 1 products: exact below 2^53
+        a = (pred[:, t] != 0).reshape(P, -1).to(torch.float64)
+        b = (gt[:, t] != 0).reshape(G, -1).to(torch.float64)
+        out += a @ b.t()
+    return out.to(torch.int64)

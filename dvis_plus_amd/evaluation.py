@@ -177,3 +177,113 @@ class VSSEvaluator:
         res = seg.result(sum(v[2] for v in videos))
         res.update(VM.VideoConsistency(self.ks).result([v[3] for v in videos]))
         return {"sem_seg": res}
+
+
+class YTVISEvaluator:
+    """YouTube-VIS / OVIS evaluation (dvis_Plus/data_video/ytvis_eval.py) with the pixel work on the device.
+
+    Same constructor and protocol as the reference (`(dataset_name, tasks=None, distributed=True, output_dir=None, *,
+    use_fast_impl=True)`, train_net_video.py passes cfg as `tasks`; use_fast_impl is accepted and ignored, as there).  The dataset
+    JSON, the dataset -> contiguous category ids and the class names come from the registered metadata (`json_file`,
+    `thing_dataset_id_to_contiguous_id`, `thing_classes`) or the keyword overrides.
+
+    process() RLE-encodes the predicted masks on the device and keeps only the strings, scores, labels and areas; when the JSON
+    has annotations it also decodes the video's ground truth there and keeps the (P, G) intersection table.  evaluate() writes
+    instances_predictions.pth and results.json exactly as the reference does (the latter byte-identical: it is what the YTVIS /
+    OVIS evaluation servers take) and returns {"segm": {AP, AP50, ..., AR10, AP-<class>}} when there are annotations, else {}."""
+
+    def __init__(self, dataset_name, tasks=None, distributed=True, output_dir=None, *, use_fast_impl=True, json_file=None,
+                 dataset_id_to_contiguous_id=None, class_names=None, device=None):
+        from . import vis_metrics as VIS
+        meta = None
+        if json_file is None or dataset_id_to_contiguous_id is None:
+            meta = _metadata(dataset_name, "json_file and dataset_id_to_contiguous_id")
+        if json_file is None:
+            json_file = meta.json_file
+        if dataset_id_to_contiguous_id is None and hasattr(meta, "thing_dataset_id_to_contiguous_id"):
+            dataset_id_to_contiguous_id = meta.thing_dataset_id_to_contiguous_id
+        if class_names is None and meta is not None:
+            class_names = meta.get("thing_classes")
+        self._id_map = dict(dataset_id_to_contiguous_id) if dataset_id_to_contiguous_id is not None else None
+        self._class_names = class_names
+        self._gt = VIS.YTVISGroundTruth(json_file)
+        self._do_evaluation = self._gt.has_annotations
+        self._distributed, self._output_dir, self._device = distributed, output_dir, device
+        self.reset()
+
+    def reset(self):
+        self._videos = []          # (prediction dicts, per-frame areas (P, T), I (P, G) or None, GT area totals, scored frames)
+
+    def process(self, inputs, outputs):
+        from . import functions as Fn
+        from . import vis_metrics as VIS
+        assert len(inputs) == 1, "More than one inputs are loaded for inference!"
+        video_id = inputs[0]["video_id"]
+        scores, labels, masks = outputs["pred_scores"], outputs["pred_labels"], outputs["pred_masks"]
+        scores = scores.tolist() if torch.is_tensor(scores) else [float(s) for s in scores]
+        labels = labels.tolist() if torch.is_tensor(labels) else [int(x) for x in labels]
+        if not torch.is_tensor(masks):
+            masks = torch.stack(list(masks)) if len(masks) else torch.zeros((0, 0, 1, 1), dtype=torch.bool)
+        dev = _device(masks, self._device)
+        masks = masks.to(dev)
+        P = len(scores)
+        if P == 0:
+            return
+        T, H, W = masks.shape[1:]
+        v = self._gt.videos.get(video_id)
+        if v is not None and (v["height"], v["width"]) != (H, W):
+            raise ValueError(f"video {video_id}: predicted masks are {H} x {W}, the dataset says {v['height']} x {v['width']}")
+        runs, run_off, area = Fn.rle_encode(masks.reshape(P * T, H, W))
+        chars, str_off = Fn.rle_strings(runs, run_off)
+        chars, str_off = chars.cpu().numpy().tobytes(), str_off.cpu().tolist()
+        area = area.view(P, T).cpu().numpy()
+        preds = []
+        for p in range(P):
+            segms = [{"size": [H, W], "counts": chars[str_off[p * T + t]:str_off[p * T + t + 1]].decode("ascii")}
+                     for t in range(T)]
+            preds.append({"video_id": video_id, "score": scores[p], "category_id": labels[p], "segmentations": segms})
+        I = ga = None
+        frames = T
+        if self._do_evaluation:
+            if v is None:
+                raise ValueError(f"video {video_id} is not in the dataset")
+            I, ga = VIS.intersections(self._gt, video_id, masks)
+            frames = min([T] + [len(a["segmentations"]) for a in self._gt.anns.get(video_id, [])])
+        self._videos.append((preds, area, I, ga, frames))
+
+    def evaluate(self):
+        import torch.distributed as dist
+        from . import vis_metrics as VIS
+        videos = [v for part in _gather(self._videos, self._distributed) for v in part]     # rank order, as comm.gather
+        predictions = [d for v in videos for d in v[0]]
+        if len(predictions) == 0:
+            return {}
+        main = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+        if self._output_dir and main:
+            os.makedirs(self._output_dir, exist_ok=True)
+            torch.save(predictions, os.path.join(self._output_dir, "instances_predictions.pth"))
+        if self._id_map is not None:
+            contiguous = list(self._id_map.values())
+            num_classes = len(contiguous)
+            assert min(contiguous) == 0 and max(contiguous) == num_classes - 1
+            reverse = {c: d for d, c in self._id_map.items()}
+            unmapped = []
+            for r in predictions:
+                assert r["category_id"] < num_classes, (f"A prediction has class={r['category_id']}, but the dataset only has "
+                                                        f"{num_classes} classes")
+                unmapped.append(dict(r, category_id=reverse[r["category_id"]]))
+            predictions = unmapped
+        if self._output_dir and main:
+            with open(os.path.join(self._output_dir, "results.json"), "w") as f:
+                f.write(json.dumps(predictions))
+        if not self._do_evaluation:
+            return {}
+        dets, tables, n = [], {}, 0
+        for preds, area, I, ga, frames in videos:
+            vid = preds[0]["video_id"]
+            idx = list(range(n, n + len(preds)))
+            for p, r in enumerate(predictions[n:n + len(preds)]):
+                dets.append(VIS.Detection(vid, r["category_id"], r["score"], area[p], n + p + 1))
+            tables[vid] = VIS.VideoTable(idx, I, area[:, :frames].sum(1), ga)
+            n += len(preds)
+        return {"segm": VIS.derive_results(VIS.evaluate(self._gt, dets, tables), self._class_names)}

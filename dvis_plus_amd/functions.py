@@ -2243,3 +2243,149 @@ def video_consistency(gt, pred, ks=(8, 16)):
                                                  native.dev_ptr(bc, "both_const"), native.stream_ptr(g.device))
     native.check(rc, "dvis_video_consistency")
     return gc, bc
+
+
+# --- VIS scoring: COCO RLE and track intersections (csrc/vis_metrics.hip) ----------------------------------------------------------
+# Same dispatch: GPU tensors run the kernels (or raise), CPU tensors take cpu_ops.py.  Masks are bool / uint8 (non-zero = set);
+# runs are int32 tensors holding COCO's uint32 run lengths (a frame has < 2^31 pixels), laid out per mask at run_off (N + 1) int64.
+RLE_ROWS = 128                 # rows per chunk of the encode table (csrc/vis_metrics.hip kRows)
+
+
+def _u8(masks, name, contiguous=True):
+    if masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)                          # same bytes, any strides
+    elif masks.dtype != torch.uint8:
+        raise RuntimeError(f"{name} must be bool or uint8 masks, got {masks.dtype}")
+    return masks.contiguous() if contiguous else masks
+
+
+def _tracks(masks, name):
+    """(masks, track stride): each track's (T, ...) frames contiguous, the tracks at any stride (a frame slice of a clip)."""
+    m = _u8(masks, name, contiguous=False)
+    if m.shape[0] and not m[0].is_contiguous():
+        m = m.contiguous()
+    return m, m.stride(0)
+
+
+def rle_encode(masks):
+    """COCO RLE of (N, H, W) masks: (runs int32, run_off (N + 1) int64, area (N) int64), on the masks' device.  The runs of mask
+    n are runs[run_off[n]:run_off[n + 1]] (column-major pixel order, zeros first)."""
+    if masks.dim() != 3:
+        raise RuntimeError(f"rle_encode: masks must be (N, H, W), got {tuple(masks.shape)}")
+    if not masks.is_cuda:
+        return cpu_ops.rle_encode(masks)
+    m = _u8(masks, "masks")
+    N, H, W = m.shape
+    dev = m.device
+    if N == 0:
+        return (torch.empty((0,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev),
+                torch.empty((0,), dtype=torch.int64, device=dev))
+    nch = (H + RLE_ROWS - 1) // RLE_ROWS
+    trans = torch.empty((N, W, nch), dtype=torch.int64, device=dev)
+    area = torch.empty((N,), dtype=torch.int64, device=dev)
+    lib = native.lib()
+    with torch.cuda.device(dev):
+        st = native.stream_ptr(dev)
+        mp = native.dev_ptr(m, "masks") if m.numel() else None
+        rc = lib.dvis_rle_encode(mp, N, H, W, 0, native.dev_ptr(trans, "trans"), native.dev_ptr(area, "area"), None, None, None,
+                                 None, st)
+        native.check(rc, "dvis_rle_encode")
+        incl = trans.view(-1).cumsum(0)
+        toff = incl - trans.view(-1)
+        moff = torch.empty((N + 1,), dtype=torch.int64, device=dev)
+        moff[:N] = toff.view(N, -1)[:, 0]
+        moff[N:] = incl[-1:]
+        total = int(moff[N])                                     # host sync: sizes the outputs
+        bnd = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
+        runs = torch.empty((total + N,), dtype=torch.int32, device=dev)
+        rc = lib.dvis_rle_encode(mp, N, H, W, 1, None, None, native.dev_ptr(toff, "toff"), native.dev_ptr(moff, "moff"),
+                                 native.dev_ptr(bnd, "bnd"), native.dev_ptr(runs, "runs") if runs.numel() else None, st)
+        native.check(rc, "dvis_rle_encode")
+    return runs, moff + torch.arange(N + 1, device=dev), area
+
+
+def rle_strings(runs, run_off):
+    """COCO's compressed `counts` strings (cocoapi rleToString) of every mask: (chars uint8, str_off (N + 1) int64) — mask n's
+    string is bytes(chars[str_off[n]:str_off[n + 1]])."""
+    if not _same_device(runs, run_off):
+        return cpu_ops.rle_strings(runs, run_off)
+    r, ro = runs.to(torch.int32).contiguous(), run_off.to(torch.int64).contiguous()
+    N = ro.numel() - 1
+    dev = r.device
+    lens = torch.empty((N,), dtype=torch.int64, device=dev)
+    lib = native.lib()
+    with torch.cuda.device(dev):
+        st = native.stream_ptr(dev)
+        rp = native.dev_ptr(r, "runs") if r.numel() else None
+        rc = lib.dvis_rle_strings(rp, native.dev_ptr(ro, "run_off"), N, None, native.dev_ptr(lens, "lens") if N else None, None,
+                                  st)
+        native.check(rc, "dvis_rle_strings")
+        str_off = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+        str_off[1:] = lens.cumsum(0)
+        chars = torch.empty((int(str_off[-1]),), dtype=torch.uint8, device=dev)
+        if chars.numel():
+            rc = lib.dvis_rle_strings(rp, native.dev_ptr(ro, "run_off"), N, native.dev_ptr(str_off, "str_off"), None,
+                                      native.dev_ptr(chars, "chars"), st)
+            native.check(rc, "dvis_rle_strings")
+    return chars, str_off
+
+
+def rle_decode(runs, run_off, H, W):
+    """(N, H, W) uint8 0 / 1 masks from COCO runs (each mask's runs must sum to H * W; checked)."""
+    if not _same_device(runs, run_off):
+        return cpu_ops.rle_decode(runs, run_off, H, W)
+    r, ro = runs.to(torch.int64), run_off.to(torch.int64).contiguous()
+    N = ro.numel() - 1
+    dev = r.device
+    cum = r.cumsum(0)
+    n_runs = ro[1:] - ro[:-1]
+    if bool((n_runs < 1).any()):
+        raise ValueError("rle_decode: every mask needs at least one run")
+    before = torch.cat((cum.new_zeros(1), cum))[ro[:-1]]          # pixels of the masks before mask n
+    if not torch.equal(cum[ro[1:] - 1] - before, torch.full_like(before, H * W)):
+        raise ValueError(f"rle_decode: a mask's runs do not sum to {H} x {W}")
+    ends = (cum - torch.repeat_interleave(before, n_runs)).to(torch.int32)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_rle_decode(native.dev_ptr(ends, "ends") if N else None, native.dev_ptr(ro, "run_off"), N, H, W,
+                                          native.dev_ptr(out, "out") if N else None, native.stream_ptr(dev))
+    native.check(rc, "dvis_rle_decode")
+    return out
+
+
+def track_intersections(pred, gt, out=None):
+    """(P, G) int64 I[p, g] = sum over frames of |pred[p, t] & gt[g, t]| for masks pred (P, T, H, W) and gt (G, T, H, W) (any
+    (T, ...) frame shape, the same on both sides).  out: an int64 (P, G) table to add to (GPU) — frame chunks of one video."""
+    if pred.shape[1:] != gt.shape[1:]:
+        raise RuntimeError(f"track_intersections: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} frames differ")
+    if not _same_device(pred, gt):
+        res = cpu_ops.track_intersections(pred, gt)
+        return res if out is None else out.add_(res)
+    (a, sa), (b, sb) = _tracks(pred, "pred"), _tracks(gt, "gt")
+    P, G, T = a.shape[0], b.shape[0], a.shape[1]
+    hw = a[0, 0].numel() if P and T else (b[0, 0].numel() if G and T else 0)
+    dev = a.device
+    acc = out is not None
+    if out is None:
+        out = torch.zeros((P, G), dtype=torch.int64, device=dev)
+    elif out.shape != (P, G) or out.dtype != torch.int64 or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"track_intersections: out must be a contiguous int64 ({P}, {G}) table on {dev}")
+    if P == 0 or G == 0 or T == 0 or hw == 0:
+        return out
+    gs = max(1, min(G, (65536 - (P + 1) * 128) // (128 + 4 * max(P, 1))))     # GT columns per launch within 64 KB of LDS
+    if P and (P + 1) * 128 + 4 * P > 65536:
+        raise RuntimeError(f"track_intersections: {P} predicted tracks exceed one launch's LDS")
+    with torch.cuda.device(dev):
+        st = native.stream_ptr(dev)
+        for g0 in range(0, G, gs):
+            g1 = min(G, g0 + gs)
+            part = out if gs >= G else torch.empty((P, g1 - g0), dtype=torch.int64, device=dev)
+            if acc and gs < G:
+                part.copy_(out[:, g0:g1])
+            rc = native.lib().dvis_track_intersections(
+                ctypes.c_void_p(a.data_ptr()), sa, P, ctypes.c_void_p(b[g0].data_ptr()), sb, g1 - g0, T, hw,
+                1 if acc else 0, native.dev_ptr(part, "out"), st)
+            native.check(rc, "dvis_track_intersections")
+            if gs < G:
+                out[:, g0:g1] = part
+    return out

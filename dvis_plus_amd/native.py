@@ -136,6 +136,10 @@ SIGNATURES = {
     "dvis_pan_pair_hist": (_i, [_p, _p, _p, _i, _i, _i, _i64, _p, _p, _p]),
     "dvis_sem_confusion": (_i, [_p, _p, _i64, _i, _p, _p, _p]),
     "dvis_video_consistency": (_i, [_p, _p, _i, _i64, _p, _i, _p, _p, _p]),
+    "dvis_rle_encode": (_i, [_p, _i64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "dvis_rle_strings": (_i, [_p, _p, _i64, _p, _p, _p, _p]),
+    "dvis_rle_decode": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
+    "dvis_track_intersections": (_i, [_p, _i64, _i, _p, _i64, _i, _i, _i64, _i, _p, _p]),
 }
 
 _lib = None

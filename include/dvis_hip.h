@@ -61,6 +61,9 @@
  *                            <- the pixel passes of the VPS / VSS scoring scripts, utils/eval_vpq_vspw.py:77-216,
  *                               utils/segmentation_and_tracking_quality.py:131-221, utils/eval_miou_vspw.py:43-56,
  *                               utils/eval_vc_vspw.py:8-23 (csrc/video_metrics.hip)
+ *   dvis_rle_encode / dvis_rle_strings / dvis_rle_decode / dvis_track_intersections
+ *                            <- the RLE and IoU passes of the VIS evaluation, data_video/ytvis_eval.py:256-293,
+ *                               ytvis_api/ytvos.py:218-287, ytvis_api/ytvoseval.py:176-222 (csrc/vis_metrics.hip)
  */
 #ifndef DVIS_HIP_H
 #define DVIS_HIP_H
@@ -722,6 +725,33 @@ int dvis_sem_confusion(const int32_t *gt, const int32_t *pred, int64_t n, int nu
  *   there too.  Outputs (nk, T) int64, entries i >= T - k zero.  2 * nk * T <= 16384. */
 int dvis_video_consistency(const int32_t *gt, const int32_t *pred, int T, int64_t HW, const int32_t *ks, int nk, int64_t *gt_const,
                            int64_t *both_const, void *stream);
+
+/*
+ * VIS scoring (csrc/vis_metrics.hip).  Masks are row-major (N, H, W) bytes (bool / uint8, non-zero = set), H * W < 2^31.  RLE is
+ * COCO's: the runs of a mask's pixels in column-major order (index x * H + y), zeros first (a leading 0 when pixel (0, 0) is set).
+ *
+ * dvis_rle_encode: replaces the per-frame mask_util.encode of data_video/ytvis_eval.py:275-280.  Two phases around a host-side
+ *   exclusive scan.  phase 0: trans (N, W, ceil(H / 128)) int64 = transitions per (mask, column, 128-row chunk), area (N) int64 =
+ *   set pixels (zeroed inside).  phase 1: toff = the exclusive scan of trans (same shape), moff (N + 1) = each mask's first
+ *   transition (moff[N] = the total); writes the transition positions to the int32 workspace bnd (moff[N] entries) and the runs,
+ *   uint32, mask n's moff[n+1] - moff[n] + 1 runs starting at runs[moff[n] + n].
+ */
+int dvis_rle_encode(const uint8_t *masks, int64_t N, int H, int W, int phase, int64_t *trans, int64_t *area, const int64_t *toff,
+                    const int64_t *moff, int32_t *bnd, uint32_t *runs, void *stream);
+/* dvis_rle_strings: the `counts` strings of ytvis_eval.py:279-283 (cocoapi rleToString) for N masks whose runs (uint32) lie at
+ *   run_off[n] .. run_off[n + 1].  chars == NULL: lens[n] = string length in bytes.  Else the string of mask n is written to
+ *   chars + str_off[n] (no terminator). */
+int dvis_rle_strings(const uint32_t *runs, const int64_t *run_off, int64_t N, const int64_t *str_off, int64_t *lens, uint8_t *chars,
+                     void *stream);
+/* dvis_rle_decode: ground-truth RLE -> masks, replacing the annToRLE / merge of ytvis_api/ytvos.py:268-287 and ytvoseval.py:206-213.
+ *   ends: per mask the cumulative run ends (int32; mask n's at run_off[n] .. run_off[n + 1], the last = H * W); out (N, H, W) uint8
+ *   0 / 1. */
+int dvis_rle_decode(const int32_t *ends, const int64_t *run_off, int64_t N, int H, int W, uint8_t *out, void *stream);
+/* dvis_track_intersections: the intersections of ytvoseval.py:203-217's iou_seq for all P x G track pairs of one video, out (P, G)
+ *   int64 = sum over frames t < T of |pred[p, t] & gt[g, t]|; frame t of track k at base + k * stride + t * HW (byte strides).
+ *   accumulate != 0 adds to out (frame chunks), else out is zeroed first.  (P + G) * 128 + P * G * 4 <= 65536. */
+int dvis_track_intersections(const uint8_t *pred, int64_t pred_stride, int P, const uint8_t *gt, int64_t gt_stride, int G, int T,
+                             int64_t HW, int accumulate, int64_t *out, void *stream);
 
 #ifdef __cplusplus
 }
