@@ -1,6 +1,6 @@
 """bench.py — frames/s of DVIS++ R50 offline inference on synthetic 720p clips (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames T] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) re-executes itself as N ranks under torch.distributed.run
@@ -15,21 +15,32 @@ reference's init rules (no checkpoints offline).  fp32 throughout (the parity ta
 runs in the product's default strict mode: a glue op that would quietly take a torch formulation on the GPU raises instead.
 
 N > 1: `value` is north_star's split (frames sharded, ONE all-gather of the per-frame queries per clip, tracker + refiner
-replicated); `owner_rounds` holds a second timed pass with stream()'s tracker-owner rounds; `dist` lists world size,
-backend and every rank's device.
+replicated); `dist` lists world size, backend and every rank's device.
 
-Also reported on the one JSON line:
+A plain run does only what the headline needs: set-up (model, clips, per-clip calibration), warm-up, the timed steps, the
+dump of --dump-outputs, the JSON line.  Also reported on that line, from the timed steps themselves:
   latency_ms    per-clip latency (first enqueue of the clip -> its outputs complete), p10 / p50 / p90 over the timed clips;
-  stages_ms     stage-synchronised breakdown of one clip (untimed extra pass);
-  candidates_100  the same workload with every non-void query sent to the panoptic stage (short second timed pass);
   roofline      the dominant hand-written kernel of the path, MSDeformAttn forward: algorithmic bytes (61 824 000 B
-                per frame-layer) / its mean launch time (HIP events on the launch stream) vs 8 TB/s.
-  roofline_tracker  the referring tracker's recurrence (its captured hipGraph replayed alone): the tracker's parameter bytes
-                x frames / replay time vs 8 TB/s — SURVEY.md §8(d)'s weight-streaming bound for the latency-bound chain.
+                per frame-layer, SURVEY.md §8d) / its mean launch time (HIP events on the launch stream) vs 8 TB/s;
+  roofline_*    the same for the other hand-written kernel families the timed steps launch (conv_x3, conv3x3, ffn, bneck,
+                mask_gemm, attn);
   dump_outputs  with --dump-outputs DIR: the arrays of the last timed step written to DIR (see dump_outputs()).
+
+--full adds everything that takes runs of its own, after the headline's timed steps (--no-extra, --no-cpu-baseline and
+--no-configs leave parts of it out):
+  owner_rounds  N > 1: a second timed pass with stream()'s tracker-owner rounds;
+  candidates_100  the same workload with every non-void query sent to the panoptic stage (short second timed pass);
+  exact_f32     the same workload with DVIS_X3=0 (short timed pass);
+  clip_by_clip  the same clips one forward() at a time (short timed pass);
+  roofline_tracker  the referring tracker's recurrence (its captured hipGraph replayed alone): the tracker's parameter bytes
+                x frames / replay time vs 8 TB/s — SURVEY.md §8(d)'s weight-streaming bound for the latency-bound chain;
+  stages_ms     stage-synchronised breakdown of one clip (untimed extra pass);
   cpu_baseline  the oracle's restatement of the reference pipeline (torch fp32 CPU ops, all host cores) on a bounded
                 sample of the same clip, in the metric's own unit, plus the oracle's C port of the MSDeformAttn kernel
-                (rank 0, N=1 only).
+                (rank 0, N=1 only);
+  configs       BASELINE.json's other single-GPU configurations as short passes (see other_configurations());
+  and in online mode, whose timed steps replay the segmenter from a hipGraph the kernel timers do not see, one more eager
+  window under the timers to price the kernels for the roofline entries.
 """
 import argparse
 import json
@@ -640,9 +651,14 @@ def main():
     ap.add_argument("--mode", default="offline", choices=["offline", "online"],
                     help="offline = BASELINE headline config (T=30, refiner on); online = config #2 (use --frames 5)")
     ap.add_argument("--candidates", type=int, default=20, help="queries sent to the panoptic stage (see main)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the untimed stage breakdown and the 100-candidate pass")
-    ap.add_argument("--no-configs", action="store_true", help="skip the short passes of BASELINE configs #2 / #4-length / #5")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run what takes runs of its own: owner rounds (N > 1), the 100-candidate, "
+                         "exact-fp32 and clip-by-clip passes, the tracker roofline, the stage breakdown, the CPU baseline, "
+                         "the other BASELINE configs (and the eager kernel-pricing window of online mode)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra passes (candidates, exact fp32, "
+                                                            "clip by clip, tracker roofline, stage breakdown, configs)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the short passes of BASELINE configs #2 / #4-length / #5")
     ap.add_argument("--backbone", default="r50", choices=["r50", "vitl", "vitb"],
                     help="r50 = the headline config; vitl = BASELINE config #5 (ViT-Adapter-L, use --queries 200)")
     ap.add_argument("--queries", type=int, default=100)
@@ -657,6 +673,7 @@ def main():
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; float32 / "
                          "float64, at most 64 MB in all: larger outputs as a fixed, seeded sample, see dump_outputs)")
     args = ap.parse_args()
+    extra = args.full and not args.no_extra      # the extra passes of a --full run (see the module docstring)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))           # one rank per GPU under torch.distributed.run; rank 0 prints the line
     # a hung collective must not hang the box: dump every thread's Python stack and exit after this many seconds
@@ -793,7 +810,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dumped = dump_outputs(outs[-1], args.dump_outputs)      # the headline pass's last step, before any other pass runs
     owner_line = None
-    if world > 1 and streamed and owner_default:
+    if args.full and world > 1 and streamed and owner_default:
         dt_o, outs_o, lat_o, _, warm_o = timed(owner_rounds=True)
         owner_line = {"value": round(args.frames * args.steps / dt_o, 3), "unit": "frames/s",
                       "ms_per_step": round(dt_o / args.steps * 1e3, 2), "warmup_clips_run": warm_o,
@@ -828,7 +845,7 @@ def main():
     # second, short timed pass: every non-void query goes to the panoptic stage (the upper end of the work that the
     # candidate count controls).  Same protocol, up to 4 clips; single GPU only.
     cand100 = None
-    if args.task == "vps" and world == 1 and not dist_on and args.candidates < args.queries and not args.no_extra:
+    if extra and args.task == "vps" and world == 1 and not dist_on and args.candidates < args.queries:
         n2 = min(4, args.steps)
         all_q = [dict(v, object_mask_threshold=0.0) for v in videos[:n2]]
         run_pass(all_q[:1])
@@ -844,7 +861,7 @@ def main():
     # the split-f16 kernels of csrc/gemm_x3.hip — the same protocol on up to 6 clips
     exact = None
     from dvis_plus_amd import functions as _Fn
-    if world == 1 and not dist_on and not args.no_extra and _Fn.X3:
+    if extra and world == 1 and not dist_on and _Fn.X3:
         n3 = min(6, args.steps)
         _Fn.X3 = False
         try:
@@ -862,7 +879,7 @@ def main():
     # fourth, short timed pass: the same clips one forward() at a time, back to back (no overlap of clip i's tracker / refiner /
     # post-processing with clip i + 1's segmenter): BASELINE.md section 3's "frames/s = T / clip latency" reading of the metric
     cbc = None
-    if world == 1 and not dist_on and not args.no_extra and streamed:
+    if extra and world == 1 and not dist_on and streamed:
         n4 = min(6, args.steps)
         streamed = False
         try:
@@ -880,7 +897,7 @@ def main():
                "latency_ms_p50": round(l4[len(l4) // 2], 2), "note": "--clip-stream 0: one forward() per clip, nothing overlapped"}
 
     timed_clips = args.steps               # clips the kernel timers saw
-    if rank == 0 and not timer.events:
+    if args.full and rank == 0 and not timer.events:
         timed_clips = 2
         # online mode replays the window's segmenter from a hipGraph: its launches do not pass the Python front-ends the timers
         # wrap.  One more (untimed) window launched eagerly, under the same timers, prices the kernels.
@@ -894,7 +911,8 @@ def main():
     if rank == 0:
         fps = T * args.steps / dt
         sec, nfr, nlaunch = timer.summary()
-        achieved = MSDA_BYTES_PER_FRAME_LAYER * nfr / sec / 1e9
+        # (no launch timed: online mode's timed steps replay the segmenter from a hipGraph; --full prices the kernels above)
+        achieved = MSDA_BYTES_PER_FRAME_LAYER * nfr / sec / 1e9 if nlaunch else None
         traffic, traffic_src = None, None     # HBM bytes per launch from the committed rocprofv3 PMC passes (bench.py cannot read PMCs itself)
         for name in ("r06b_msda_traffic.json", "r06_msda_traffic.json", "r05_msda_traffic.json", "r03_msda_traffic.json", "r02_msda_traffic.json", "r01_msda_traffic.json"):
             tj = os.path.join(ROOT, "profiles", name)
@@ -1035,7 +1053,7 @@ def main():
             "latency_ms": {"p10": pct(0.1), "p50": pct(0.5), "p90": pct(0.9), "n": len(ms),
                            "note": "clip handed to the model -> its outputs complete (HIP events); under clip streaming a "
                                    "clip waits one segmenter pass of the previous clip"},
-            "roofline": {"bound": "hbm", "kernel": "msda_fwd (fused MSDeformAttn forward)",
+            "roofline": None if not nlaunch else {"bound": "hbm", "kernel": "msda_fwd (fused MSDeformAttn forward)",
                          "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                          "traffic_source": traffic_src,
@@ -1073,15 +1091,15 @@ def main():
             res["owner_rounds"] = owner_line
         if cand100 is not None:
             res["candidates_100"] = cand100
-        if world == 1 and not dist_on and not args.no_extra:
+        if extra and world == 1 and not dist_on:
             trk_roof = tracker_roofline(model)
             if trk_roof is not None:
                 res["roofline_tracker"] = trk_roof
-        if world == 1 and not dist_on and args.mode == "offline" and not args.no_extra:
+        if extra and world == 1 and not dist_on and args.mode == "offline":
             res["stages_ms"] = stage_breakdown(model, videos[0], args.task)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(model, clips[0], thr=videos[0].get("object_mask_threshold", 0.8))
-        if world == 1 and not dist_on and not args.no_extra and not args.no_configs and args.mode == "offline" \
+        if extra and world == 1 and not dist_on and not args.no_configs and args.mode == "offline" \
                 and args.backbone == "r50" and T == 30 and len(clips) >= 2:
             res["configs"] = other_configurations(model, clips, device, args)
         print(json.dumps(res))

@@ -34,6 +34,21 @@ def test_gpus_flag_without_launcher_reexecs(monkeypatch):
     assert calls == [4] and e.value.code == 7          # the launcher's exit code is bench.py's exit code
 
 
+def test_full_flag_parses_and_reaches_every_rank(monkeypatch):
+    """--full (the extra passes: owner rounds, exact fp32, CPU baseline, configs, ...) is an option of every run and is handed
+    unchanged to the ranks that --gpus N starts."""
+    import bench
+    seen = {}
+    monkeypatch.setattr(bench, "self_launch", lambda n: seen.setdefault("argv", list(sys.argv)) and 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--steps", "3", "--full", "--no-cpu-baseline"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 0 and seen["argv"][1:] == ["--gpus", "2", "--steps", "3", "--full", "--no-cpu-baseline"]
+    cmd, _ = bench.launch_command(2, seen["argv"][1:], n_devices=2, port=29778)
+    assert cmd[-6:] == ["--gpus", "2", "--steps", "3", "--full", "--no-cpu-baseline"]
+
+
 def test_self_launch_runs_the_launch_command(monkeypatch):
     import subprocess
     import bench

@@ -63,9 +63,10 @@ def test_bench_self_launches_two_ranks_on_one_gpu(tmp_path):
     reference's analogue is detectron2's launch(main, args.num_gpus), train_net_video.py:322-329).  On a one-GPU box the ranks
     share the device over gloo and the line says so; what is asserted is everything the first RCCL run will need to get
     right above the transport: rc 0, ONE JSON line from rank 0, dist.world_size == 2, both measurements present (the
-    headline = north_star's split, and `owner_rounds`), the metric and the workload of BASELINE.json."""
+    headline = north_star's split, and `owner_rounds`, a pass of its own that only --full runs), the metric and the workload
+    of BASELINE.json."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extra"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extra"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     tail = "\n".join((r.stdout + r.stderr).splitlines()[-25:])

@@ -4,14 +4,15 @@
 # split-f16 kernels, the bench lines of every configuration, the per-rank emulation.
 #   STAGE=1 bench lines + kernel stats + steady table;  STAGE=2 PMC passes;  STAGE=3 rank emulation;  default: all
 mkdir -p gpurun_out/r05
+L=${BENCH_LINES:-bench_lines}; mkdir -p "$L"      # where this script's bench JSON lines go (bench.py --full: every extra pass)
 S=${STAGE:-0}
 if [ "$S" = "0" ] || [ "$S" = "1" ]; then
   python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > gpurun_out/r05/smoke.txt 2>&1
-  python bench.py > gpurun_out/r05/r05_bench_line.json 2> gpurun_out/r05/r05_bench_line.err
-  cut -c1-200 gpurun_out/r05/r05_bench_line.json
+  python bench.py --full > "$L/r05_bench_line.json" 2> "$L/r05_bench_line.err"
+  cut -c1-200 "$L/r05_bench_line.json"
   PMC=0 bash tools/prof.sh r05_bench python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > /dev/null 2>&1
   bash tools/exp/steady.sh r05 > /dev/null 2>&1
-  python bench.py --mode online --frames 5 --steps 20 --warmup 4 --no-cpu-baseline --no-extra > gpurun_out/r05/r05_bench_line_online_T5.json 2>/dev/null
+  python bench.py --full --mode online --frames 5 --steps 20 --warmup 4 --no-cpu-baseline --no-extra > "$L/r05_bench_line_online_T5.json" 2>/dev/null
   python bench.py --frames 64 --steps 6 --warmup 2 --no-cpu-baseline --no-extra > gpurun_out/r05/r05_bench_line_T64.json 2>/dev/null
   python bench.py --backbone vitl --queries 200 --steps 4 --warmup 2 --no-cpu-baseline --no-extra > gpurun_out/r05/r05_bench_line_vitl_200q.json 2>/dev/null
   python bench.py --task vis --no-cpu-baseline --no-extra > gpurun_out/r05/r05_bench_line_vis.json 2>/dev/null

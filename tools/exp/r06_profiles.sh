@@ -5,6 +5,7 @@
 # (-> r06_x3_traffic.json: what bench.py's roofline_conv_x3 / roofline_ffn `traffic` reads).
 #   STAGE=1 bench line + kernel stats + steady tables;  STAGE=2 PMC passes;  default: both
 mkdir -p gpurun_out/r06
+L=${BENCH_LINES:-bench_lines}; mkdir -p "$L"      # where this script's bench JSON lines go (bench.py --full: every extra pass)
 S=${STAGE:-0}
 if [ "$S" = "0" ] || [ "$S" = "2" ]; then
   PMC_LIGHT=1 timeout 600 bash tools/prof.sh r06_pd python tools/pd_only.py pixel_decoder 5 > /dev/null 2>&1
@@ -18,8 +19,8 @@ if [ "$S" = "0" ] || [ "$S" = "2" ]; then
 fi
 if [ "$S" = "0" ] || [ "$S" = "1" ]; then
   python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" > gpurun_out/r06/smoke.txt 2>&1
-  (time python bench.py) > gpurun_out/r06/r06_bench_line.json 2> gpurun_out/r06/r06_bench_line.err
-  cut -c1-200 gpurun_out/r06/r06_bench_line.json
+  (time python bench.py --full) > "$L/r06_bench_line.json" 2> "$L/r06_bench_line.err"
+  cut -c1-200 "$L/r06_bench_line.json"
   PMC=0 bash tools/prof.sh r06_bench python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > /dev/null 2>&1
   cp gpurun_out/prof/r06_bench_kernel_stats.csv gpurun_out/r06/r06_bench_kernel_stats.csv 2>/dev/null
   grep "^{" gpurun_out/prof/r06_bench_run.log | cut -c1-3000 > gpurun_out/r06/r06_bench_line_under_rocprof.json 2>/dev/null
