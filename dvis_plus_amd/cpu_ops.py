@@ -183,3 +183,41 @@ def track_intersections(pred, gt):
         b = (gt[:, t] != 0).reshape(G, -1).to(torch.float64)
         out += a @ b.t()
     return out.to(torch.int64)
+
+
+# --- prediction files (csrc/pred_write.hip): segment stats and painted maps by plain torch ops -------------------------------------
+def pan_segment_stats(pan, n):
+    """((T, n + 1, 5) int64 area, xmin, ymin, xmax, ymax per frame and id 0..n — all zero where the id has no pixel, bad): the
+    ids of the (T, H, W) map outside 0..n are only counted in `bad`."""
+    T, H, W = pan.shape
+    ids = pan.reshape(T, H * W).long()
+    ok = (ids >= 0) & (ids <= n)
+    bad = int((~ok).sum())
+    key = (torch.arange(T).view(T, 1) * (n + 1) + ids.clamp(0, n))[ok]
+    pos = torch.arange(H * W).expand(T, H * W)[ok]
+    xs, ys = pos % W, pos // W
+    out = torch.zeros((T * (n + 1), 5), dtype=torch.int64)
+    out[:, 0] = torch.bincount(key, minlength=T * (n + 1))
+    big = torch.full((T * (n + 1),), H * W, dtype=torch.int64)
+    out[:, 1] = big.scatter_reduce(0, key, xs, "amin")
+    out[:, 2] = big.scatter_reduce(0, key, ys, "amin")
+    out[:, 3] = torch.zeros_like(big).scatter_reduce(0, key, xs, "amax")
+    out[:, 4] = torch.zeros_like(big).scatter_reduce(0, key, ys, "amax")
+    out[out[:, 0] == 0] = 0
+    return out.view(T, n + 1, 5), bad
+
+
+def pan_paint_rgb(pan, lut):
+    """(T, H, W, 3) uint8: the colour lut[id] (0x00BBGGRR int32, one per id) of every pixel; ids outside the table are black."""
+    ids = pan.long()
+    ok = (ids >= 0) & (ids < lut.numel())
+    col = torch.where(ok, lut.long()[ids.clamp(0, max(lut.numel() - 1, 0))] if lut.numel() else torch.zeros_like(ids), 0)
+    return torch.stack((col & 255, (col >> 8) & 255, (col >> 16) & 255), -1).to(torch.uint8)
+
+
+def sem_paint(sem, lut):
+    """(uint8 lut[sem & 255] of every pixel, bad (256) int64): lut (256) holds the dataset id of each class byte or -1 (no mapping:
+    written as 255, counted per class)."""
+    c = sem.long() & 255
+    d = lut.long()[c]
+    return torch.where(d >= 0, d, 255).to(torch.uint8), torch.bincount(c[d < 0].reshape(-1), minlength=256)

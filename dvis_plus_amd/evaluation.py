@@ -11,6 +11,9 @@ ground truth themselves and return the scripts' final numbers from evaluate():
 process() accepts the product's device outputs or their `to_reference_format` CPU form (copied to the device).  Per-video
 statistics are kept with the video's position in the dataset, gathered over torch.distributed in evaluate() and reduced in
 video order, so a run on N ranks gives the numbers of a run on one.  d2.install() does not register these classes.
+
+The writers of the files the VIPSeg / VSPW evaluation servers take (VPSPredictionWriter, VSSPredictionWriter, for test splits
+without ground truth) live in pred_writers.py and are re-exported here.
 """
 import json
 import os
@@ -287,3 +290,6 @@ class YTVISEvaluator:
             tables[vid] = VIS.VideoTable(idx, I, area[:, :frames].sum(1), ga)
             n += len(preds)
         return {"segm": VIS.derive_results(VIS.evaluate(self._gt, dets, tables), self._class_names)}
+
+
+from .pred_writers import PanopticIdGenerator, VPSPredictionWriter, VSSPredictionWriter  # noqa: E402,F401  (re-export)

@@ -2389,3 +2389,68 @@ def track_intersections(pred, gt, out=None):
             if gs < G:
                 out[:, g0:g1] = part
     return out
+
+
+# --- prediction files: segment stats and painted maps (csrc/pred_write.hip) -------------------------------------------------------
+# Same dispatch: GPU tensors run the kernels (or raise), CPU tensors take cpu_ops.py.  Maps are (T, H, W) integer tensors, made
+# contiguous int32 (and 16-byte aligned for the paint kernels) first.
+def _i32_aligned(t, name):
+    m = _i32(t, name)
+    return m if m.data_ptr() % 16 == 0 else m.clone()
+
+
+def pan_segment_stats(pan, n):
+    """(stats, bad): stats (T, n + 1, 5) int64 = area, xmin, ymin, xmax, ymax of every id 0..n in every frame (inclusive pixel
+    coordinates, all zero where the id has no pixel); bad = the number of pixels whose id lies outside 0..n (an int on the CPU, a
+    one-element int64 tensor on the GPU, read without a host sync)."""
+    if pan.dim() != 3:
+        raise RuntimeError(f"pan_segment_stats: the map must be (T, H, W), got {tuple(pan.shape)}")
+    n = int(n)
+    if not pan.is_cuda:
+        return cpu_ops.pan_segment_stats(pan, n)
+    T, H, W = pan.shape
+    m = _i32(pan, "pan")
+    out = torch.empty((T, n + 1, 5), dtype=torch.int64, device=m.device)
+    bad = torch.empty((1,), dtype=torch.int64, device=m.device)
+    with torch.cuda.device(m.device):
+        rc = native.lib().dvis_pan_segment_stats(native.dev_ptr(m, "pan") if m.numel() else None, T, H, W, n,
+                                                 native.dev_ptr(out, "out"), native.dev_ptr(bad, "bad"),
+                                                 native.stream_ptr(m.device))
+    native.check(rc, "dvis_pan_segment_stats")
+    return out, bad
+
+
+def pan_paint_rgb(pan, lut):
+    """(T, H, W, 3) uint8 RGB of a (T, H, W) id map: colour lut[id] (int32 0x00BBGGRR per id 0..len(lut) - 1), black for ids
+    outside the table."""
+    if pan.dim() != 3:
+        raise RuntimeError(f"pan_paint_rgb: the map must be (T, H, W), got {tuple(pan.shape)}")
+    if not _same_device(pan, lut):
+        return cpu_ops.pan_paint_rgb(pan, lut)
+    m, lt = _i32_aligned(pan, "pan"), _i32(lut.reshape(-1), "lut")
+    out = torch.empty((*m.shape, 3), dtype=torch.uint8, device=m.device)
+    if m.numel():
+        with torch.cuda.device(m.device):
+            rc = native.lib().dvis_pan_paint_rgb(native.dev_ptr(m, "pan"), m.numel(),
+                                                 native.dev_ptr(lt, "lut") if lt.numel() else None, lt.numel(),
+                                                 native.dev_ptr(out, "out"), native.stream_ptr(m.device))
+        native.check(rc, "dvis_pan_paint_rgb")
+    return out
+
+
+def sem_paint(sem, lut):
+    """(out, bad): out = uint8 lut[sem & 255] (same shape as sem), lut (256) int = the dataset id 0..255 of each class byte or -1;
+    bad (256) int64 = per class byte, the pixels that had no mapping (written as 255)."""
+    if lut.numel() != 256:
+        raise RuntimeError(f"sem_paint: lut must have 256 entries, got {lut.numel()}")
+    if not _same_device(sem, lut):
+        return cpu_ops.sem_paint(sem, lut)
+    m, lt = _i32_aligned(sem, "sem"), _i32(lut.reshape(-1), "lut")
+    out = torch.empty(m.shape, dtype=torch.uint8, device=m.device)
+    bad = torch.empty((256,), dtype=torch.int64, device=m.device)
+    with torch.cuda.device(m.device):
+        rc = native.lib().dvis_sem_paint(native.dev_ptr(m, "sem") if m.numel() else None, m.numel(), native.dev_ptr(lt, "lut"),
+                                         native.dev_ptr(out, "out") if m.numel() else None, native.dev_ptr(bad, "bad"),
+                                         native.stream_ptr(m.device))
+    native.check(rc, "dvis_sem_paint")
+    return out, bad

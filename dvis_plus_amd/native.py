@@ -140,6 +140,9 @@ SIGNATURES = {
     "dvis_rle_strings": (_i, [_p, _p, _i64, _p, _p, _p, _p]),
     "dvis_rle_decode": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
     "dvis_track_intersections": (_i, [_p, _i64, _i, _p, _i64, _i, _i, _i64, _i, _p, _p]),
+    "dvis_pan_segment_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
+    "dvis_pan_paint_rgb": (_i, [_p, _i64, _p, _i, _p, _p]),
+    "dvis_sem_paint": (_i, [_p, _i64, _p, _p, _p, _p]),
 }
 
 _lib = None

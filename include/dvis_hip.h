@@ -64,6 +64,9 @@
  *   dvis_rle_encode / dvis_rle_strings / dvis_rle_decode / dvis_track_intersections
  *                            <- the RLE and IoU passes of the VIS evaluation, data_video/ytvis_eval.py:256-293,
  *                               ytvis_api/ytvos.py:218-287, ytvis_api/ytvoseval.py:176-222 (csrc/vis_metrics.hip)
+ *   dvis_pan_segment_stats / dvis_pan_paint_rgb / dvis_sem_paint
+ *                            <- the pixel passes of the VIPSeg / VSPW prediction writers, data_video/vps_eval.py:112-143,
+ *                               data_video/vss_eval.py:93-100 (csrc/pred_write.hip)
  */
 #ifndef DVIS_HIP_H
 #define DVIS_HIP_H
@@ -752,6 +755,25 @@ int dvis_rle_decode(const int32_t *ends, const int64_t *run_off, int64_t N, int 
  *   accumulate != 0 adds to out (frame chunks), else out is zeroed first.  (P + G) * 128 + P * G * 4 <= 65536. */
 int dvis_track_intersections(const uint8_t *pred, int64_t pred_stride, int P, const uint8_t *gt, int64_t gt_stride, int G, int T,
                              int64_t HW, int accumulate, int64_t *out, void *stream);
+
+/*
+ * Prediction files (csrc/pred_write.hip): integer only, run-to-run identical.  Maps are contiguous (T, H, W) int32; the paint
+ * kernels take them as one flat run of npx = T * H * W pixels and need `map` and `out` 16-byte aligned.
+ *
+ * dvis_pan_segment_stats: replaces the per-segment `pan_seg_result == id`, mask[i].sum() and np.where bbox of
+ *   data_video/vps_eval.py:112-143.  out (T, n + 1, 5) int64 = per frame and id 0..n: area, xmin, ymin, xmax, ymax (inclusive
+ *   pixel coordinates; all five zero where the id has no pixel).  bad (one int64) = pixels whose id lies outside 0..n (the
+ *   reference ignores ids that segments_infos does not list).  Outputs are zeroed inside.  H * W < 2^31, n < 2^30.
+ */
+int dvis_pan_segment_stats(const int32_t *map, int T, int H, int W, int n, int64_t *out, int64_t *bad, void *stream);
+/* dvis_pan_paint_rgb: replaces `pan_format[mask] = color` of data_video/vps_eval.py:121-123.  out (npx, 3) uint8 = the colour
+ *   lut[id] (0x00BBGGRR, nlut entries) of every pixel as r, g, b bytes; ids outside 0..nlut - 1 become (0, 0, 0). */
+int dvis_pan_paint_rgb(const int32_t *map, int64_t npx, const int32_t *lut, int nlut, uint8_t *out, void *stream);
+/* dvis_sem_paint: replaces the astype(np.uint8) and per-class id mapping of data_video/vss_eval.py:93-100.  out (npx) uint8 =
+ *   lut[map & 255], lut (256 int32, device) = the dataset id 0..255 of each class byte (255 for the ignore label), or -1 when the
+ *   class has no mapping: such pixels are written as 255 and counted in bad[class] (256 int64, zeroed inside), so the host can
+ *   raise the reference's KeyError. */
+int dvis_sem_paint(const int32_t *map, int64_t npx, const int32_t *lut, uint8_t *out, int64_t *bad, void *stream);
 
 #ifdef __cplusplus
 }
