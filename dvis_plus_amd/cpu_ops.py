@@ -221,3 +221,29 @@ def sem_paint(sem, lut):
     c = sem.long() & 255
     d = lut.long()[c]
     return torch.where(d >= 0, d, 255).to(torch.uint8), torch.bincount(c[d < 0].reshape(-1), minlength=256)
+
+
+# --- test-time frame resize (csrc/frame_resize.hip): Pillow's BILINEAR resample as gathers and integer sums ------------------------
+def _resample_axis(x, tab, dim):
+    """One pass of Pillow's 8-bit resample along `dim` of the int64 tensor x: tab (n_out, k + 2) = first index, taps, k
+    coefficients (zero past the taps, so clamped gathers there add nothing)."""
+    n_in = x.shape[dim]
+    first, coef = tab[:, 0].long(), tab[:, 2:].long()
+    n_out, k = coef.shape
+    idx = (first[:, None] + torch.arange(k)[None]).clamp(max=n_in - 1)
+    g = x.index_select(dim, idx.reshape(-1))
+    g = g.reshape(*x.shape[:dim], n_out, k, *x.shape[dim + 1:])
+    c = coef.reshape(n_out, k, *([1] * (x.dim() - dim - 1)))
+    acc = (g * c).sum(dim + 1) + (1 << 21)
+    return torch.where(acc <= 0, 0, (acc >> 22).clamp(max=255))
+
+
+def resize_frames_u8(frames, xtab, ytab, reverse=False):
+    """(T, 3, h, w) uint8 from (T, H, W, 3) uint8: horizontal pass (xtab) then vertical pass (ytab), each clip8 to uint8 values,
+    as Pillow's ImagingResample does; channels reversed if `reverse`."""
+    out = []
+    for f in frames:
+        x = _resample_axis(f.long(), xtab, 1)
+        x = _resample_axis(x, ytab, 0)
+        out.append((x.flip(-1) if reverse else x).permute(2, 0, 1).to(torch.uint8))
+    return torch.stack(out)

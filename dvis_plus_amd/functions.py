@@ -2454,3 +2454,96 @@ def sem_paint(sem, lut):
                                          native.stream_ptr(m.device))
     native.check(rc, "dvis_sem_paint")
     return out, bad
+
+
+# --- test-time frame resize (csrc/frame_resize.hip) ------------------------------------------------------------------------------
+# detectron2's ResizeTransform.apply_image = Pillow Image.resize(BILINEAR) on uint8 frames.  Pillow's 8-bit resample is integer
+# fixed point over per-axis coefficient tables (Resample.c precompute_coeffs + normalize_coeffs_8bpc); resize_tables restates
+# them in the same double arithmetic, and both the kernel and the CPU formulation take them from here.
+_RESIZE_PRECISION = 22
+_resize_dev_tables = {}
+_resize_lock = threading.Lock()
+
+
+def _resize_host_table(n_in, n_out):
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    rows = []
+    for o in range(n_out):
+        center = (o + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = []
+        for x in range(xmax):
+            t = abs((x + xmin - center + 0.5) * ss)
+            w.append(1.0 - t if t < 1.0 else 0.0)
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        rows.append([xmin, xmax] + [int(0.5 + v * (1 << _RESIZE_PRECISION)) for v in w] + [0] * (ksize - xmax))
+    return torch.tensor(rows, dtype=torch.int32)
+
+
+def resize_tables(n_in, n_out, device=None):
+    """(n_out, k + 2) int32 table of one axis of Pillow's BILINEAR resample of n_in -> n_out pixels: per output index the first
+    input index, the number of taps and k fixed-point (2^22) coefficients, zero past the taps.  k = 2 * ceil(max(n_in / n_out, 1))
+    + 1.  Cached per (n_in, n_out) and per device; callers must not modify it."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise RuntimeError(f"resize_tables: sizes must be positive, got {n_in} -> {n_out}")
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (n_in, n_out, dev)
+    tab = _resize_dev_tables.get(key)
+    if tab is None:
+        host = _resize_dev_tables.get((n_in, n_out, torch.device("cpu")))
+        if host is None:
+            host = _resize_host_table(n_in, n_out)
+        tab = host if dev.type == "cpu" else host.to(dev)
+        with _resize_lock:
+            _resize_dev_tables.setdefault((n_in, n_out, torch.device("cpu")), host)
+            tab = _resize_dev_tables.setdefault(key, tab)
+    return tab
+
+
+def resize_frames_u8(frames, size, reverse_channels=False):
+    """(T, 3, h, w) uint8 CHW: every (H, W, 3) uint8 frame of `frames` (T, H, W, 3) resized to size = (h, w) exactly as
+    Image.fromarray(frame).resize((w, h), Image.BILINEAR) does (byte-identical), channels reversed if reverse_channels
+    (BGR <-> RGB, which commutes with the resize).  GPU tensors run csrc/frame_resize.hip (or raise), CPU tensors the torch
+    formulation of cpu_ops.py over the same tables.  Frames taller than 100 x their width are rejected (Pillow resizes those in
+    the other order)."""
+    if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+        raise RuntimeError(f"resize_frames_u8: frames must be a uint8 tensor, got "
+                           f"{frames.dtype if torch.is_tensor(frames) else type(frames).__name__}")
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"resize_frames_u8: frames must be (T, H, W, 3), got {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise RuntimeError("resize_frames_u8: frames must be contiguous")
+    T, H, W, _ = frames.shape
+    h, w = (int(v) for v in size)
+    if T == 0 or H == 0 or W == 0:
+        raise RuntimeError(f"resize_frames_u8: no pixels to resize, frames {tuple(frames.shape)}")
+    if h < 1 or w < 1:
+        raise RuntimeError(f"resize_frames_u8: the output size must be positive, got {(h, w)}")
+    if H > 100 * W:
+        raise RuntimeError(f"resize_frames_u8: frames of {H}x{W} (taller than 100 x their width) are not supported")
+    if H * W * 3 >= 2 ** 31 or h * w * 3 >= 2 ** 31 or T > 65535:
+        raise RuntimeError(f"resize_frames_u8: too large: T {T}, {H}x{W} -> {h}x{w}")
+    xtab, ytab = resize_tables(W, w, frames.device), resize_tables(H, h, frames.device)
+    if not frames.is_cuda:
+        return cpu_ops.resize_frames_u8(frames, xtab, ytab, reverse_channels)
+    x = frames if frames.data_ptr() % 16 == 0 else frames.clone()
+    out = torch.empty((T, 3, h, w), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = native.lib().dvis_resize_frames_u8(native.dev_ptr(x, "frames"), T, H, W, native.dev_ptr(out, "out"), h, w,
+                                                native.dev_ptr(xtab, "xtab"), xtab.shape[1] - 2,
+                                                native.dev_ptr(ytab, "ytab"), ytab.shape[1] - 2, int(bool(reverse_channels)),
+                                                native.stream_ptr(x.device))
+    native.check(rc, "dvis_resize_frames_u8")
+    return out

@@ -143,6 +143,7 @@ SIGNATURES = {
     "dvis_pan_segment_stats": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "dvis_pan_paint_rgb": (_i, [_p, _i64, _p, _i, _p, _p]),
     "dvis_sem_paint": (_i, [_p, _i64, _p, _p, _p, _p]),
+    "dvis_resize_frames_u8": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p]),
 }
 
 _lib = None

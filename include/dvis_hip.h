@@ -67,6 +67,10 @@
  *   dvis_pan_segment_stats / dvis_pan_paint_rgb / dvis_sem_paint
  *                            <- the pixel passes of the VIPSeg / VSPW prediction writers, data_video/vps_eval.py:112-143,
  *                               data_video/vss_eval.py:93-100 (csrc/pred_write.hip)
+ *   dvis_resize_frames_u8    <- the test-time ResizeShortestEdge of the demo / eval loaders: detectron2's
+ *                               ResizeTransform.apply_image (Pillow BILINEAR on uint8) as called by demo_video/predictor.py:246
+ *                               and data_video/dataset_mapper.py:333, plus the [:, :, ::-1] and transpose(2, 0, 1) around it
+ *                               (csrc/frame_resize.hip)
  */
 #ifndef DVIS_HIP_H
 #define DVIS_HIP_H
@@ -774,6 +778,18 @@ int dvis_pan_paint_rgb(const int32_t *map, int64_t npx, const int32_t *lut, int 
  *   class has no mapping: such pixels are written as 255 and counted in bad[class] (256 int64, zeroed inside), so the host can
  *   raise the reference's KeyError. */
 int dvis_sem_paint(const int32_t *map, int64_t npx, const int32_t *lut, uint8_t *out, int64_t *bad, void *stream);
+
+/*
+ * dvis_resize_frames_u8 (csrc/frame_resize.hip): Pillow's 8-bit BILINEAR resample (ImagingResample, PRECISION_BITS = 22) of
+ *   T uint8 HWC frames in (T, H, W, 3) to out (T, 3, h, w) uint8 CHW, byte-identical to Image.resize((w, h), BILINEAR).
+ *   xtab (w, kx + 2) / ytab (h, ky + 2) int32 (device): per output index [first input index, taps, kx / ky fixed-point
+ *   coefficients], Pillow's precompute_coeffs + normalize_coeffs_8bpc (built on the host: functions.resize_tables).  Horizontal
+ *   pass first, vertical second, each clip8(2^21 + sum in * coef); an unchanged axis takes the identity table [x, 2, 2^22, 0].
+ *   reverse != 0: plane c of the output is input channel 2 - c (BGR <-> RGB).  `in` and `out` 16-byte aligned.  Integer only,
+ *   run-to-run identical.  DVIS_E_UNSUPPORTED when a 4 x 1 output tile's inputs exceed 64 KB of LDS (down-scales by ~100x).
+ */
+int dvis_resize_frames_u8(const uint8_t *in, int T, int H, int W, uint8_t *out, int h, int w, const int32_t *xtab, int kx,
+                          const int32_t *ytab, int ky, int reverse, void *stream);
 
 #ifdef __cplusplus
 }
