@@ -247,3 +247,40 @@ def resize_frames_u8(frames, xtab, ytab, reverse=False):
         x = _resample_axis(x, ytab, 0)
         out.append((x.flip(-1) if reverse else x).permute(2, 0, 1).to(torch.uint8))
     return torch.stack(out)
+
+
+# --- set criterion (csrc/criterion.hip): matching cost and point-sampled mask losses on CPU tensors -----------------------------
+def point_sample_rows(rows, coords):
+    """rows (R, H, W) any real dtype, coords (R, P, 2) normalised (x, y) -> (R, P) fp32: bilinear, zero padding, pixel centres at
+    (i + 0.5) / size (grid_sample on 2 c - 1, align_corners=False)."""
+    R, P = coords.shape[:2]
+    if R == 0 or P == 0:
+        return (rows.to(torch.float32).sum() * 0).expand(R, P).clone() if rows.requires_grad \
+            else torch.zeros((R, P), dtype=torch.float32, device=coords.device)
+    grid = (2.0 * coords.to(torch.float32) - 1.0)[:, :, None, :]
+    return F.grid_sample(rows.to(torch.float32)[:, None], grid, mode="bilinear", padding_mode="zeros",
+                         align_corners=False)[:, 0, :, 0]
+
+
+def match_cost_terms(pred, tgt, coords, logits, tgt_ids):
+    """pred (Q, T, H, W), tgt (G, T, Ht, Wt), coords (K, 2) shared by every mask and frame, logits (Q, C), tgt_ids (G) ->
+    (cost_class, cost_mask, cost_dice), each (Q, G), unweighted."""
+    Q, T, H, W = pred.shape
+    G, K = tgt.shape[0], coords.shape[0]
+    x = point_sample_rows(pred.reshape(Q * T, H, W), coords[None].expand(Q * T, K, 2)).reshape(Q, T * K)
+    t = point_sample_rows(tgt.reshape(G * T, *tgt.shape[2:]), coords[None].expand(G * T, K, 2)).reshape(G, T * K)
+    cost_class = -logits.to(torch.float32).softmax(-1)[:, tgt_ids.to(torch.int64)]
+    cost_mask = (F.softplus(-x) @ t.T + F.softplus(x) @ (1.0 - t).T) / (T * K)
+    s = x.sigmoid()
+    cost_dice = 1.0 - (2.0 * (s @ t.T) + 1.0) / (s.sum(-1)[:, None] + t.sum(-1)[None, :] + 1.0)
+    return cost_class, cost_mask, cost_dice
+
+
+def point_loss_sums(src, tgt, coords):
+    """src, tgt (R, H, W), coords (R, P, 2) -> (R, 3): per row sum_p bce(x, t), sum_p sigmoid(x) t, sum_p sigmoid(x) + sum_p t over
+    the sampled values (differentiable in src through torch autograd)."""
+    x = point_sample_rows(src, coords)
+    t = point_sample_rows(tgt, coords)
+    s = x.sigmoid()
+    bce = F.softplus(x) - x * t
+    return torch.stack((bce.sum(-1), (s * t).sum(-1), s.sum(-1) + t.sum(-1)), dim=-1)

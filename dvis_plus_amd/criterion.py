@@ -1,0 +1,183 @@
+"""Set-prediction criterion of Mask2Former / DVIS++ with the reference's names, constructor arguments and loss-dict contract
+(mask2former_video/modeling/criterion.py: VideoSetCriterion; mask2former/modeling/criterion.py: SetCriterion), and
+``build_criterion(cfg, meta_arch)`` = the criterion part of the reference's three ``from_config``s.
+
+``loss_masks`` runs on the fused HIP kernels for GPU tensors (functions.point_sample for the oversampling pass, torch.topk,
+functions.point_mask_losses forward + backward) and on the torch formulations of cpu_ops.py for CPU tensors; ``loss_labels`` is
+torch's cross_entropy ((B, Q, C + 1): not a hot path).  Half / bf16 mask logits are upcast to fp32 BEFORE sampling (the reference
+samples in half and upcasts after).  Every random draw goes through ``_rand`` in the reference's order and shapes:
+(R, int(num_points * oversample_ratio), 2) then (R, num_points - int(importance_sample_ratio * num_points), 2) per loss_masks.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import functions as Fn
+from .matcher import HungarianMatcher, VideoHungarianMatcher, VideoHungarianMatcher_Consistent
+
+
+def _world_size():
+    d = torch.distributed
+    return d.get_world_size() if d.is_available() and d.is_initialized() else 1
+
+
+class VideoSetCriterion(nn.Module):
+    """1) Hungarian assignment between the targets and the outputs, 2) classification and mask losses of the matched pairs.
+    outputs: "pred_logits" (B, Q, C + 1), "pred_masks" (B, Q, T, H, W), optionally "aux_outputs": a list of such dicts.
+    targets[b]: "labels" (G), "masks" (G, T, H, W)."""
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                 importance_sample_ratio, frames=2):
+        super().__init__()
+        self.num_classes = num_classes
+        self.matcher = matcher
+        self.weight_dict = weight_dict
+        self.eos_coef = eos_coef
+        self.losses = losses
+        empty_weight = torch.ones(self.num_classes + 1)
+        empty_weight[-1] = self.eos_coef
+        self.register_buffer("empty_weight", empty_weight)
+        self.num_points = num_points
+        self.oversample_ratio = oversample_ratio
+        self.importance_sample_ratio = importance_sample_ratio
+        self.frames = frames
+
+    def _rand(self, shape, device):
+        """Every random draw of the criterion: override to replay recorded draws."""
+        return torch.rand(shape, device=device)
+
+    def loss_labels(self, outputs, targets, indices, num_masks):
+        logits = outputs["pred_logits"].float()
+        idx = self._get_src_permutation_idx(indices)
+        matched = torch.cat([t["labels"][J.to(t["labels"].device)] for t, (_, J) in zip(targets, indices)])
+        classes = torch.full(logits.shape[:2], self.num_classes, dtype=torch.int64, device=logits.device)
+        classes[idx] = matched.to(classes)
+        return {"loss_ce": F.cross_entropy(logits.transpose(1, 2), classes, self.empty_weight)}
+
+    def _matched_rows(self, outputs, targets, indices):
+        """(src rows (R, H, W), target rows (R, H, W)) of the matched pairs, frames flattened into rows."""
+        src = outputs["pred_masks"][self._get_src_permutation_idx(indices)]
+        tgt = torch.cat([t["masks"][J.to(t["masks"].device)] for t, (_, J) in zip(targets, indices)])
+        return src.flatten(0, 1), tgt.flatten(0, 1)
+
+    def uncertain_point_coords(self, src_rows):
+        """detectron2's get_uncertain_point_coords_with_randomness with uncertainty -|logit|: of int(num_points * oversample_ratio)
+        uniform points per row keep the int(importance_sample_ratio * num_points) most uncertain, fill up with uniform points."""
+        R, dev = src_rows.shape[0], src_rows.device
+        n_sampled = int(self.num_points * self.oversample_ratio)
+        n_uncertain = int(self.importance_sample_ratio * self.num_points)
+        n_random = self.num_points - n_uncertain
+        coords = self._rand((R, n_sampled, 2), dev)
+        uncertainty = -Fn.point_sample(src_rows, coords).abs()
+        idx = torch.topk(uncertainty, k=n_uncertain, dim=1)[1]
+        picked = torch.gather(coords, 1, idx[:, :, None].expand(R, n_uncertain, 2))
+        if n_random > 0:
+            picked = torch.cat([picked, self._rand((R, n_random, 2), dev)], dim=1)
+        return picked
+
+    def loss_masks(self, outputs, targets, indices, num_masks):
+        src_rows, tgt_rows = self._matched_rows(outputs, targets, indices)
+        with torch.no_grad():
+            coords = self.uncertain_point_coords(src_rows)
+        loss_mask, loss_dice = Fn.point_mask_losses(src_rows, tgt_rows.to(src_rows.device), coords, num_masks)
+        return {"loss_mask": loss_mask, "loss_dice": loss_dice}
+
+    def _get_src_permutation_idx(self, indices):
+        batch_idx = torch.cat([torch.full_like(src, i) for i, (src, _) in enumerate(indices)])
+        return batch_idx, torch.cat([src for (src, _) in indices])
+
+    def _get_tgt_permutation_idx(self, indices):
+        batch_idx = torch.cat([torch.full_like(tgt, i) for i, (_, tgt) in enumerate(indices)])
+        return batch_idx, torch.cat([tgt for (_, tgt) in indices])
+
+    def get_loss(self, loss, outputs, targets, indices, num_masks):
+        loss_map = {"labels": self.loss_labels, "masks": self.loss_masks}
+        assert loss in loss_map, f"do you really want to compute {loss} loss?"
+        return loss_map[loss](outputs, targets, indices, num_masks)
+
+    def forward(self, outputs, targets, matcher_outputs=None, ret_match_result=False):
+        """-> dict of losses ("loss_ce", "loss_mask", "loss_dice" and their "_i" copies per aux_outputs entry) [, indices].
+        matcher_outputs: match on these outputs instead (once; the aux layers then reuse the pairs)."""
+        matched_on = outputs if matcher_outputs is None else matcher_outputs
+        indices = self.matcher({k: v for k, v in matched_on.items() if k != "aux_outputs"}, targets)
+        num_masks = torch.as_tensor([sum(len(t["labels"]) for t in targets)], dtype=torch.float,
+                                    device=next(iter(outputs.values())).device)
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.all_reduce(num_masks)
+        num_masks = torch.clamp(num_masks / _world_size(), min=1).item()
+
+        losses = {}
+        for loss in self.losses:
+            losses.update(self.get_loss(loss, outputs, targets, indices, num_masks))
+        for i, aux in enumerate(outputs.get("aux_outputs", ())):
+            if matcher_outputs is None:
+                indices = self.matcher(aux, targets)
+            for loss in self.losses:
+                losses.update({f"{k}_{i}": v for k, v in self.get_loss(loss, aux, targets, indices, num_masks).items()})
+        return (losses, indices) if ret_match_result else losses
+
+    def __repr__(self):
+        body = [f"matcher: {self.matcher.__repr__(_repr_indent=8)}"] + [
+            f"{k}: {getattr(self, k)}" for k in ("losses", "weight_dict", "num_classes", "eos_coef", "num_points",
+                                                  "oversample_ratio", "importance_sample_ratio")]
+        return "\n".join(["Criterion " + self.__class__.__name__] + [" " * 4 + line for line in body])
+
+
+class SetCriterion(VideoSetCriterion):
+    """The image model's criterion: "pred_masks" (B, Q, H, W), targets[b]["masks"] (G_b, H_b, W_b), zero-padded to one size."""
+
+    def __init__(self, num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                 importance_sample_ratio):
+        super().__init__(num_classes, matcher, weight_dict, eos_coef, losses, num_points, oversample_ratio,
+                         importance_sample_ratio)
+        del self.frames
+
+    def _matched_rows(self, outputs, targets, indices):
+        src = outputs["pred_masks"][self._get_src_permutation_idx(indices)]
+        H = max(t["masks"].shape[-2] for t in targets)
+        W = max(t["masks"].shape[-1] for t in targets)
+        rows = []
+        for t, (_, J) in zip(targets, indices):
+            m = t["masks"][J.to(t["masks"].device)]
+            rows.append(F.pad(m, (0, W - m.shape[-1], 0, H - m.shape[-2])))
+        return src, torch.cat(rows)
+
+    def forward(self, outputs, targets):
+        return super().forward(outputs, targets)
+
+
+def build_criterion(cfg, meta_arch=None):
+    """The criterion the reference's ``from_config`` of `meta_arch` builds (MODEL.META_ARCHITECTURE when None): "MinVIS"
+    (dvis_Plus/meta_architecture.py:105-138), "DVIS_Plus_online" (:516-571), "DVIS_Plus_offline" (:1175-1243), "MaskFormer"
+    (mask2former/maskformer_model.py:100-162) — matcher class, weights, weight_dict with its deep-supervision copies, losses."""
+    meta_arch = cfg.MODEL.META_ARCHITECTURE if meta_arch is None else meta_arch
+    if not isinstance(meta_arch, str):
+        meta_arch = getattr(meta_arch, "__name__", type(meta_arch).__name__)
+    mf = cfg.MODEL.MASK_FORMER
+    weights = {"cost_class": mf.CLASS_WEIGHT, "cost_mask": mf.MASK_WEIGHT, "cost_dice": mf.DICE_WEIGHT}
+    num_points, use_cl = mf.TRAIN_NUM_POINTS, False
+    if meta_arch == "MinVIS":
+        matcher = VideoHungarianMatcher(num_points=num_points, **weights)
+    elif meta_arch == "DVIS_Plus_online":
+        matcher = VideoHungarianMatcher_Consistent(num_points=num_points, frames=cfg.INPUT.SAMPLING_FRAME_NUM, **weights)
+        use_cl = getattr(cfg.MODEL.TRACKER, "USE_CL", False)
+    elif meta_arch == "DVIS_Plus_offline":
+        # the T frames of a clip are flattened into one (T h, w) image there: T times the points
+        num_points = num_points * cfg.INPUT.SAMPLING_FRAME_NUM
+        matcher = VideoHungarianMatcher(num_points=num_points, **weights)
+        use_cl = getattr(cfg.MODEL.REFINER, "USE_CL", False)
+    elif meta_arch == "MaskFormer":
+        matcher = HungarianMatcher(num_points=num_points, **weights)
+    else:
+        raise ValueError(f"build_criterion: no criterion recipe for META_ARCHITECTURE {meta_arch!r}")
+    weight_dict = {"loss_ce": mf.CLASS_WEIGHT, "loss_mask": mf.MASK_WEIGHT, "loss_dice": mf.DICE_WEIGHT}
+    if mf.DEEP_SUPERVISION:
+        base = dict(weight_dict)
+        for i in range(mf.DEC_LAYERS - 1):
+            weight_dict.update({f"{k}_{i}": v for k, v in base.items()})
+    if use_cl:
+        weight_dict["loss_reid"] = 2
+    cls = SetCriterion if meta_arch == "MaskFormer" else VideoSetCriterion
+    return cls(cfg.MODEL.SEM_SEG_HEAD.NUM_CLASSES, matcher=matcher, weight_dict=weight_dict, eos_coef=mf.NO_OBJECT_WEIGHT,
+               losses=["labels", "masks"], num_points=num_points, oversample_ratio=mf.OVERSAMPLE_RATIO,
+               importance_sample_ratio=mf.IMPORTANCE_SAMPLE_RATIO)

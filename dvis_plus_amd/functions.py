@@ -2547,3 +2547,201 @@ def resize_frames_u8(frames, size, reverse_channels=False):
                                                 native.stream_ptr(x.device))
     native.check(rc, "dvis_resize_frames_u8")
     return out
+
+
+# --- set criterion: matching cost and point-sampled mask losses (csrc/criterion.hip) ---------------------------------------------
+# Dispatch by device like every op here: a GPU tensor runs the HIP kernel or the call raises (DVIS_STRICT=0 opts out: the torch
+# formulation then runs on the GPU), a CPU tensor takes cpu_ops.py.  Masks may be strided views (the decoders return such): ONE
+# .contiguous() copy is made here, the kernels see contiguous maps.  Half / bf16 predictions are upcast to fp32 BEFORE sampling.
+# Reproducible backward of the point losses: 1 = always, 0 = never, default = when torch.use_deterministic_algorithms(True) is set.
+POINT_LOSS_BWD_DETERMINISTIC = os.environ.get("DVIS_POINT_LOSS_BWD_DETERMINISTIC")
+
+
+def _unserved(op, x, why):
+    """A GPU tensor the criterion kernels do not serve: raise under the strict default — with or without autograd, these kernels
+    have a backward —, else (DVIS_STRICT=0) let the caller take the torch formulation."""
+    if x.is_cuda and os.environ.get("DVIS_STRICT", "1") != "0":
+        raise RuntimeError(f"DVIS_STRICT: {op} would run its torch formulation on a GPU tensor ({why}; shape "
+                           f"{tuple(x.shape)}, dtype {x.dtype})")
+    return True
+
+
+def _pred_f32(x, op):
+    """fp32 / fp16 / bf16 predictions -> fp32 (upcast before sampling); anything else is not served."""
+    if x.dtype in (torch.float16, torch.bfloat16):
+        return x.float(), True
+    return x, x.dtype == torch.float32
+
+
+def _target_maps(t, device):
+    """Target masks -> (contiguous tensor the kernels read, is-bytes flag): bool / uint8 stay bytes, fp32 stays, the rest -> fp32."""
+    if t.device != device:
+        t = t.to(device)
+    if t.dtype == torch.bool:
+        return t.contiguous().view(torch.uint8), 1
+    if t.dtype == torch.uint8:
+        return t.contiguous(), 1
+    return t.to(torch.float32).contiguous(), 0
+
+
+def _coords_f32(c, device):
+    return c.to(device=device, dtype=torch.float32).contiguous()
+
+
+@fp32_island
+def match_cost(pred_masks, tgt_masks, coords, logits, tgt_ids, cost_class=1.0, cost_mask=1.0, cost_dice=1.0,
+               return_terms=False):
+    """The matching cost of VideoHungarianMatcher / HungarianMatcher for one batch element (matcher.py:107-151).
+    pred_masks (Q, T, H, W) or (Q, H, W) mask logits; tgt_masks (G, T, Ht, Wt) / (G, Ht, Wt) fp32, uint8 or bool, at their own size; coords (K, 2) or
+    (1, K, 2) normalised (x, y) shared by all masks and frames; logits (Q, C); tgt_ids (G) integer class ids.
+    -> C (Q, G) fp32 = cost_mask * m + cost_class * c + cost_dice * d  [, terms (3, Q, G) = (c, m, d) unweighted]."""
+    if pred_masks.dim() == 3:
+        pred_masks, tgt_masks = pred_masks[:, None], tgt_masks[:, None]
+    if pred_masks.dim() != 4 or tgt_masks.dim() != 4 or pred_masks.shape[1] != tgt_masks.shape[1]:
+        raise RuntimeError(f"match_cost: pred_masks {tuple(pred_masks.shape)} and tgt_masks {tuple(tgt_masks.shape)} must be "
+                           "(Q, T, H, W) and (G, T, Ht, Wt)")
+    Q, T, H, W = pred_masks.shape
+    G, _, Ht, Wt = tgt_masks.shape
+    coords = coords.reshape(-1, 2)
+    K = coords.shape[0]
+    if logits.dim() != 2 or logits.shape[0] != Q or tgt_ids.shape != (G,):
+        raise RuntimeError(f"match_cost: logits {tuple(logits.shape)} / tgt_ids {tuple(tgt_ids.shape)} do not fit Q {Q}, G {G}")
+    if K == 0 or T == 0 or H * W == 0 or Ht * Wt == 0:
+        raise RuntimeError("match_cost: no sample points / empty maps")
+    dev = pred_masks.device
+    pred, served = _pred_f32(pred_masks.detach(), "match_cost")
+    logits = logits.detach()
+    if G == 0 or Q == 0:
+        C = torch.zeros((Q, G), dtype=torch.float32, device=dev)
+        return (C, torch.zeros((3, Q, G), dtype=torch.float32, device=dev)) if return_terms else C
+    if not dev.type == "cuda" or (not served and _unserved("match_cost", pred_masks, "dtype not fp32 / fp16 / bf16")):
+        c, m, d = cpu_ops.match_cost_terms(pred.to(torch.float32), tgt_masks.to(dev), coords.to(dev), logits.to(dev),
+                                           tgt_ids.to(dev))
+        C = cost_mask * m + cost_class * c + cost_dice * d
+        return (C, torch.stack((c, m, d))) if return_terms else C
+    pred = pred.contiguous()
+    tgt, u8 = _target_maps(tgt_masks, dev)
+    co, lg = _coords_f32(coords, dev), logits.to(device=dev, dtype=torch.float32).contiguous()
+    ids = tgt_ids.to(device=dev, dtype=torch.int64).contiguous()
+    C = torch.empty((Q, G), dtype=torch.float32, device=dev)
+    terms = torch.empty((3, Q, G), dtype=torch.float32, device=dev) if return_terms else None
+    ws = torch.empty((native.lib().dvis_match_cost_ws_bytes(Q, G, T, K) + 3) // 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_match_cost(native.dev_ptr(pred, "pred_masks"), native.dev_ptr(tgt, "tgt_masks"), u8,
+                                          native.dev_ptr(co, "coords"), native.dev_ptr(lg, "logits"),
+                                          native.dev_ptr(ids, "tgt_ids"), Q, G, T, H, W, Ht, Wt, K, lg.shape[1], float(cost_class),
+                                          float(cost_mask), float(cost_dice), native.dev_ptr(C, "C"),
+                                          native.dev_ptr(terms, "terms") if return_terms else None,
+                                          native.dev_ptr(ws, "ws"), native.stream_ptr(dev))
+    native.check(rc, "dvis_match_cost")
+    return (C, terms) if return_terms else C
+
+
+@fp32_island
+def point_sample(rows, coords):
+    """detectron2's point_sample(input (R, 1, H, W), point_coords (R, P, 2), align_corners=False) for one-channel rows:
+    rows (R, H, W) fp32 / fp16 / bf16 / uint8 / bool, coords (R, P, 2) -> (R, P) fp32.  No gradient."""
+    if rows.dim() != 3 or coords.dim() != 3 or coords.shape[0] != rows.shape[0] or coords.shape[2] != 2:
+        raise RuntimeError(f"point_sample: rows {tuple(rows.shape)} must be (R, H, W) and coords {tuple(coords.shape)} (R, P, 2)")
+    R, H, W = rows.shape
+    P = coords.shape[1]
+    dev = rows.device
+    rows = rows.detach()
+    if H * W == 0:
+        raise RuntimeError("point_sample: empty maps")
+    byte = rows.dtype in (torch.bool, torch.uint8)
+    x, served = (rows, True) if byte else _pred_f32(rows, "point_sample")
+    if dev.type != "cuda" or (not served and _unserved("point_sample", rows, "dtype not served")):
+        with torch.no_grad():
+            return cpu_ops.point_sample_rows(x, coords.to(dev))
+    x, u8 = _target_maps(x, dev)
+    co = _coords_f32(coords, dev)
+    out = torch.empty((R, P), dtype=torch.float32, device=dev)
+    if R * P == 0:
+        return out
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_point_sample_rows(native.dev_ptr(x, "rows"), u8, native.dev_ptr(co, "coords"), R, P, H, W,
+                                                 native.dev_ptr(out, "out"), native.stream_ptr(dev))
+    native.check(rc, "dvis_point_sample_rows")
+    return out
+
+
+def _losses_from_sums(sums, P, num_masks):
+    loss_mask = (sums[:, 0] / P).sum() / num_masks
+    loss_dice = (1.0 - (2.0 * sums[:, 1] + 1.0) / (sums[:, 2] + 1.0)).sum() / num_masks
+    return loss_mask, loss_dice
+
+
+class PointMaskLossFunction(Function):
+    """(loss_mask, loss_dice) of sigmoid_ce_loss + dice_loss on point-sampled rows (criterion.py:21-67) on the HIP kernels;
+    gradient to src only."""
+
+    @staticmethod
+    def forward(ctx, src, tgt, tgt_u8, coords, num_masks, deterministic):
+        R, H, W = src.shape
+        Ht, Wt = tgt.shape[1:]
+        P = coords.shape[1]
+        dev = src.device
+        sums = torch.empty((R, 3), dtype=torch.float32, device=dev)
+        if R:
+            ws = torch.empty((native.lib().dvis_point_loss_ws_bytes(R) + 3) // 4, dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                rc = native.lib().dvis_point_loss_fwd(native.dev_ptr(src, "src"), native.dev_ptr(tgt, "tgt"), tgt_u8,
+                                                      native.dev_ptr(coords, "coords"), R, P, H, W, Ht, Wt,
+                                                      native.dev_ptr(sums, "sums"), native.dev_ptr(ws, "ws"),
+                                                      native.stream_ptr(dev))
+            native.check(rc, "dvis_point_loss_fwd")
+        ctx.save_for_backward(src, tgt, coords, sums)
+        ctx.args = (tgt_u8, float(num_masks), deterministic)
+        return _losses_from_sums(sums, P, float(num_masks))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_mask, g_dice):
+        src, tgt, coords, sums = ctx.saved_tensors
+        tgt_u8, num_masks, deterministic = ctx.args
+        R, H, W = src.shape
+        Ht, Wt = tgt.shape[1:]
+        P = coords.shape[1]
+        dev = src.device
+        grad = torch.empty_like(src)
+        if R:
+            gm = g_mask.to(torch.float32).reshape(1).contiguous()
+            gd = g_dice.to(torch.float32).reshape(1).contiguous()
+            if deterministic is None:
+                deterministic = (POINT_LOSS_BWD_DETERMINISTIC == "1") if POINT_LOSS_BWD_DETERMINISTIC in ("0", "1") \
+                    else torch.are_deterministic_algorithms_enabled()
+            acc = torch.empty((R * H * W,), dtype=torch.int64, device=dev) if deterministic else None
+            with torch.cuda.device(dev):
+                rc = native.lib().dvis_point_loss_bwd(native.dev_ptr(src, "src"), native.dev_ptr(tgt, "tgt"), tgt_u8,
+                                                      native.dev_ptr(coords, "coords"), native.dev_ptr(sums, "sums"),
+                                                      native.dev_ptr(gm, "g_mask"), native.dev_ptr(gd, "g_dice"), R, P, H, W,
+                                                      Ht, Wt, num_masks, native.dev_ptr(grad, "grad_src"),
+                                                      native.dev_ptr(acc, "det_ws") if deterministic else None,
+                                                      native.stream_ptr(dev))
+            native.check(rc, "dvis_point_loss_bwd")
+        return grad, None, None, None, None, None
+
+
+@fp32_island
+def point_mask_losses(src, tgt, coords, num_masks, deterministic=None):
+    """loss_mask = sum_r mean_p bce(x, t) / num_masks and loss_dice = sum_r (1 - (2 a + 1) / (b + 1)) / num_masks of the matched
+    rows: src (R, H, W) mask logits (fp32; fp16 / bf16 are upcast before sampling), tgt (R, Ht, Wt) fp32 / uint8 / bool (its own size),
+    coords (R, P, 2) normalised (x, y) per row, num_masks a positive float.  Differentiable in src only.  Two 0-d tensors, formed
+    on the device without a host sync.  deterministic: the backward's reproducible form (see POINT_LOSS_BWD_DETERMINISTIC)."""
+    if src.dim() != 3 or tgt.dim() != 3 or tgt.shape[0] != src.shape[0] or coords.dim() != 3 or coords.shape[0] != src.shape[0] or coords.shape[2] != 2:
+        raise RuntimeError(f"point_mask_losses: src {tuple(src.shape)}, tgt {tuple(tgt.shape)} must be (R, H, W), (R, Ht, Wt) and coords "
+                           f"{tuple(coords.shape)} (R, P, 2)")
+    num_masks = float(num_masks)
+    P = coords.shape[1]
+    if not num_masks > 0 or P == 0 or src.shape[1] * src.shape[2] == 0 or tgt.shape[1] * tgt.shape[2] == 0:
+        raise RuntimeError("point_mask_losses: num_masks must be positive, P > 0 and the maps non-empty")
+    dev = src.device
+    x, served = _pred_f32(src, "point_mask_losses")
+    if dev.type != "cuda" or (not served and _unserved("point_mask_losses", src, "dtype not fp32 / fp16 / bf16")):
+        sums = cpu_ops.point_loss_sums(x.to(torch.float32), tgt.to(dev).detach(), coords.to(dev).detach())
+        return _losses_from_sums(sums, P, num_masks)
+    if src.shape[0] >= 65536:
+        raise RuntimeError(f"point_mask_losses: {src.shape[0]} rows (at most 65535 per call)")
+    t, u8 = _target_maps(tgt.detach(), dev)
+    return PointMaskLossFunction.apply(x.contiguous(), t, u8, _coords_f32(coords.detach(), dev), num_masks, deterministic)

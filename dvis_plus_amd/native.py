@@ -144,6 +144,12 @@ SIGNATURES = {
     "dvis_pan_paint_rgb": (_i, [_p, _i64, _p, _i, _p, _p]),
     "dvis_sem_paint": (_i, [_p, _i64, _p, _p, _p, _p]),
     "dvis_resize_frames_u8": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _i, _i, _p]),
+    "dvis_match_cost_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "dvis_match_cost": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _p, _p, _p, _p]),
+    "dvis_point_sample_rows": (_i, [_p, _i, _p, _i64, _i, _i, _i, _p, _p]),
+    "dvis_point_loss_ws_bytes": (_i64, [_i64]),
+    "dvis_point_loss_fwd": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "dvis_point_loss_bwd": (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
 }
 
 _lib = None

@@ -42,6 +42,9 @@
  *   dvis_vss_argmax          <- two-stage resize + sigmoid + einsum("qc,qthw->cthw") + max(0) of inference_video_vss,
  *                               dvis_Plus/meta_architecture.py:954-979
  *   dvis_lsap_solve          <- scipy.optimize.linear_sum_assignment as called by Noiser.match_embds, dvis_Plus/noiser.py:43-56
+ *   dvis_match_cost / dvis_point_sample_rows / dvis_point_loss_fwd / dvis_point_loss_bwd
+ *                            <- the matching cost and the point-sampled mask losses of the set criterion (training),
+ *                               mask2former_video/modeling/matcher.py:107-151, criterion.py:21-67
  *   dvis_match_chain         <- the frame-by-frame matching loop of ReferringTracker_noiser.forward, dvis_Plus/tracker.py:210-291
  *   dvis_gemm_nt             <- the projections around every attention / FFN block of the tracker and the refiner
  *                               (nn.MultiheadAttention in/out_proj, linear1/2, MLP: dvis_Plus/tracker.py:293-318,
@@ -790,6 +793,42 @@ int dvis_sem_paint(const int32_t *map, int64_t npx, const int32_t *lut, uint8_t 
  */
 int dvis_resize_frames_u8(const uint8_t *in, int T, int H, int W, uint8_t *out, int h, int w, const int32_t *xtab, int kx,
                           const int32_t *ytab, int ky, int reverse, void *stream);
+
+/*
+ * Set-prediction supervision (csrc/criterion.hip): the matching cost of VideoHungarianMatcher / HungarianMatcher
+ * (mask2former_video/modeling/matcher.py:107-151) and the point-sampled mask losses of VideoSetCriterion / SetCriterion
+ * (mask2former_video/modeling/criterion.py:21-67, :150-200).  Sampling everywhere is F.grid_sample(x, 2 c - 1, bilinear, zeros,
+ * align_corners=False) at normalised points c = (x, y) in [0, 1]: pixel coordinate c * W - 0.5, taps outside the map are zero.
+ * fp32 arithmetic; every map is contiguous; a target map is fp32 (tgt_u8 = 0) or one byte per pixel (uint8 / bool, tgt_u8 = 1).
+ * Every forward result is run-to-run identical (fixed split of the points, partials added in index order, no float atomics).
+ *
+ * A prediction map is H x W, a target map Ht x Wt (the targets are at the padded image's size, the predictions at a quarter of
+ * it): both are sampled at the same normalised points.
+ * dvis_match_cost: pred (Q, T, H, W), tgt (G, T, Ht, Wt), coords (K, 2) shared by all masks and frames, logits (Q, NC),
+ *   tgt_ids (G) int64 in [0, NC) ->  C (Q, G) = w_mask * cost_mask + w_class * cost_class + w_dice * cost_dice  and, when terms is
+ *   not null, terms (3, Q, G) = [cost_class, cost_mask, cost_dice] unweighted:  cost_class = -softmax(logits)[q, ids[g]],
+ *   cost_mask = sum_n (softplus(-x) t + softplus(x) (1 - t)) / (T K),  cost_dice = 1 - (2 sum sigmoid(x) t + 1) / (sum sigmoid(x) +
+ *   sum t + 1)  over the T K sampled values x of query q and t of target g.  ws: dvis_match_cost_ws_bytes(Q, G, T, K) bytes.
+ * dvis_point_sample_rows: rows (R, H, W) fp32 or bytes, coords (R, P, 2) -> out (R, P) fp32.
+ * dvis_point_loss_fwd: src (R, H, W), tgt (R, Ht, Wt), coords (R, P, 2) -> out (R, 3) = per row [sum_p bce(x, t),
+ *   a = sum_p sigmoid(x) t, b = sum_p sigmoid(x) + sum_p t].  ws: dvis_point_loss_ws_bytes(R) bytes.  R < 65536.
+ * dvis_point_loss_bwd: grad_src (R, H, W) (zeroed inside, by a kernel) of  g_mask * sum_r mean_p bce / num_masks + g_dice *
+ *   sum_r (1 - (2 a + 1) / (b + 1)) / num_masks;  sums = the forward's out, g_mask / g_dice = one DEVICE float each.  det_ws null:
+ *   fp32 vector atomics (last bits vary run to run); det_ws = R * H * W * 8 bytes (8-byte aligned): 64-bit fixed-point
+ *   accumulation, the same bits every run (targets in [0, 1]).
+ */
+int64_t dvis_match_cost_ws_bytes(int Q, int G, int T, int K);
+int dvis_match_cost(const float *pred, const void *tgt, int tgt_u8, const float *coords, const float *logits,
+                    const int64_t *tgt_ids, int Q, int G, int T, int H, int W, int Ht, int Wt, int K, int NC, float w_class,
+                    float w_mask, float w_dice, float *C, float *terms, void *ws, void *stream);
+int dvis_point_sample_rows(const void *rows, int rows_u8, const float *coords, int64_t R, int P, int H, int W, float *out,
+                           void *stream);
+int64_t dvis_point_loss_ws_bytes(int64_t R);
+int dvis_point_loss_fwd(const float *src, const void *tgt, int tgt_u8, const float *coords, int R, int P, int H, int W, int Ht, int Wt,
+                        float *out, void *ws, void *stream);
+int dvis_point_loss_bwd(const float *src, const void *tgt, int tgt_u8, const float *coords, const float *sums, const float *g_mask,
+                        const float *g_dice, int R, int P, int H, int W, int Ht, int Wt, float num_masks, float *grad_src,
+                        void *det_ws, void *stream);
 
 #ifdef __cplusplus
 }
