@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import functions as Fn
+from . import derived, functions as Fn
 from .registry import BACKBONE_REGISTRY, ShapeSpec
 
 
@@ -39,19 +39,23 @@ class ConvBN(nn.Conv2d):
     def __init__(self, cin, cout, k, stride=1, padding=0):
         super().__init__(cin, cout, k, stride=stride, padding=padding, bias=False)
         self.norm = FrozenBatchNorm2d(cout)
-        self._folded = None
+        self._folded = derived.Derived()
         nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
 
     def folded(self):
-        key = (self.weight._version, self.norm.weight._version, self.norm.running_var._version, self.weight.device,
-               self.weight.is_contiguous(memory_format=torch.channels_last))
-        if self._folded is None or self._folded[0] != key:
-            scale, shift = self.norm.scale_shift()
+        n, cl = self.norm, self.weight.is_contiguous(memory_format=torch.channels_last)
+
+        def make():
+            scale, shift = n.scale_shift()
             w = (self.weight.detach() * scale.reshape(-1, 1, 1, 1))
-            if key[-1]:
+            if cl:
                 w = w.contiguous(memory_format=torch.channels_last)
-            self._folded = (key, w, shift.detach().contiguous())
-        return self._folded[1], self._folded[2]
+            return w, shift.detach().contiguous()
+        return self._folded.get([self.weight, n.weight, n.bias, n.running_mean, n.running_var], make, (cl,))
+
+    def is_folded_weight(self, t):
+        """Is `t` the folded weight of this layer (the range guard names a layer by the weight it packed)?"""
+        return self._folded.value is not None and self._folded.value[0] is t
 
     def forward(self, x, res=None, relu=False):
         """conv (MIOpen, no bias) then ONE fused pass: + folded-BN shift (+ residual) (+ ReLU)."""

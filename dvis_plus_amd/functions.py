@@ -18,7 +18,7 @@ import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
-from . import cpu_ops, native
+from . import cpu_ops, derived, native
 from .cpu_ops import ms_deform_attn_core_pytorch    # noqa: F401  (the reference's name for the CPU-tensor formulation, ms_deform_attn_func.py:52)
 
 
@@ -1038,7 +1038,7 @@ class _X3RangeGuard:
                 for pn, prm in list(mod.named_parameters(recurse=False)) + list(mod.named_buffers(recurse=False)):
                     if prm is wt:
                         name = f"{n}.{pn}"
-                if name is None and getattr(mod, "_folded", None) is not None and mod._folded[1] is wt:
+                if name is None and getattr(mod, "is_folded_weight", lambda t: False)(wt):
                     name = f"{n} (FrozenBN folded)"
                 if name:
                     break
@@ -1094,50 +1094,42 @@ X3_CONV_XEXP = int(os.environ.get("DVIS_X3_CONV_XEXP", "2"))
 X3_CONV1X1_MIN_CI = int(os.environ.get("DVIS_X3_CONV1X1_MIN_CI", "64"))
 
 
-class _PackCache:
-    """Packed forms of weights, made once per (weight, kind of pack, weight version).  Keyed by (id(weight), kind) — the same
-    tensor packed two ways (linear and FFN, 1x1 and 3x3) keeps both — with least-recently-used eviction past `cap` entries
-    (a cleared-at-once dict re-packed every layer of every forward once a process held more than `cap` weights; each pack
-    reads max|w| back to the host)."""
-
-    def __init__(self, cap=4096):
-        from collections import OrderedDict
-        self.cap, self.d, self.lock = cap, OrderedDict(), threading.Lock()
-
-    def get(self, key_obj, kind, version_key, make):
-        k = (id(key_obj), kind)
-        with self.lock:                # (stream()'s phase-B thread and the main thread both pack: the LRU order is shared state)
-            ent = self.d.get(k)
-            if ent is None or ent[0] != version_key:
-                tag = ent[3] if ent is not None else X3_GUARD.new_tag(key_obj, kind)
-                self.d[k] = ent = (version_key, make(), key_obj, tag)       # (holds key_obj: id() stays unique)
-                while len(self.d) > self.cap:
-                    self.d.popitem(last=False)
-            else:
-                self.d.move_to_end(k)
-        # the launch that follows carries this weight's tag (range guard; per host thread) — and the device's guard word exists
-        X3_GUARD.word(key_obj.device)
-        native.lib().dvis_x3_set_tag(ent[3])
-        return ent[1]
-
-    def __len__(self):
-        return len(self.d)
-
-    def clear(self):
-        self.d.clear()
-
-
-_X3_PACKED = _PackCache()
-
-
 def _x3_exp(w):
     """e with max|w| * 2^e in [2^13, 2^14): the weight fills the f16 range, its low term stays a normal number."""
     m = float(w.detach().abs().max())
     return 0 if m == 0.0 or m != m else 14 - math.frexp(m)[1]
 
 
-def _x3_cache(key_obj, version_key, make, kind="linear"):
-    return _X3_PACKED.get(key_obj, kind, version_key, make)
+def _x3_cache(key_obj, sources, make, kind="linear"):
+    """The split-f16 pack `make()` of `sources`, one per (key_obj, kind) in derived.TABLE; every pack has its own range-guard tag."""
+    ent = derived.TABLE.entry(key_obj, kind, sources, make, note=lambda: X3_GUARD.new_tag(key_obj, kind))
+    # the launch that follows carries this weight's tag (range guard; per host thread) — and the device's guard word exists
+    X3_GUARD.word(key_obj.device)
+    native.lib().dvis_x3_set_tag(ent.note)
+    return ent.value
+
+
+def _x3_packed(w, nbytes, pack, name):
+    """(packed uint8 buffer of `nbytes`, wexp) of the contiguous weight `w` through `pack(wexp, buffer pointer, stream)`."""
+    e = _x3_exp(w)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        native.check(pack(e, ctypes.c_void_p(buf.data_ptr()), native.stream_ptr(w.device)), name)
+    return buf, e
+
+
+def _x3_pack_conv1x1(w2):
+    """(packed buffer, wexp) of a contiguous (Co, Ci) matrix for csrc/conv1x1_x3.hip."""
+    Co, Ci = w2.shape
+    return _x3_packed(w2, native.lib().dvis_conv1x1_x3_packed_bytes(Ci, Co), lambda e, buf, st: native.lib().dvis_conv1x1_x3_pack(
+        native.dev_ptr(w2, "weight"), Co, Ci, e, buf, st), "dvis_conv1x1_x3_pack")
+
+
+def _x3_pack_conv3x3(w4):
+    """The same of a contiguous (Co, Ci, 3, 3) weight (nine taps)."""
+    Co, Ci = w4.shape[:2]
+    return _x3_packed(w4, native.lib().dvis_conv3x3_x3_packed_bytes(Ci, Co), lambda e, buf, st: native.lib().dvis_conv3x3_x3_pack(
+        native.dev_ptr(w4, "weight"), Co, Ci, e, buf, st), "dvis_conv3x3_x3_pack")
 
 
 def x3_pack(weight):
@@ -1150,13 +1142,9 @@ def x3_pack(weight):
         nbytes = native.lib().dvis_x3_packed_bytes(N, K)
         if nbytes <= 0:
             raise RuntimeError(f"x3_pack: weight {tuple(w.shape)} is not served (K % 32 == 0)")
-        e = _x3_exp(w)
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            native.check(native.lib().dvis_x3_pack(ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e,
-                                                   ctypes.c_void_p(buf.data_ptr()), native.stream_ptr(w.device)), "dvis_x3_pack")
-        return buf, e
-    return _x3_cache(weight, (weight._version, weight.data_ptr(), weight.device, tuple(weight.shape)), make)
+        return _x3_packed(w, nbytes, lambda e, buf, st: native.lib().dvis_x3_pack(
+            ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e, buf, st), "dvis_x3_pack")
+    return _x3_cache(weight, [weight], make)
 
 
 # The large-K tall GEMMs (ViT blocks: K = 1024 .. 4096, N a multiple of 256) take the TILED split-f16 kernel (csrc/gemm_x3_tile.hip:
@@ -1181,15 +1169,9 @@ def x3_tile_pack(weight, order=0):
         nbytes = native.lib().dvis_x3_tile_packed_bytes(N, K)
         if nbytes <= 0:
             raise RuntimeError(f"x3_tile_pack: weight {tuple(w.shape)} is not served (N % 256 == 0, K % 32 == 0)")
-        e = _x3_exp(w)
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        with torch.cuda.device(w.device):
-            native.check(native.lib().dvis_x3_tile_pack_order(ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e, order,
-                                                              ctypes.c_void_p(buf.data_ptr()), native.stream_ptr(w.device)),
-                         "dvis_x3_tile_pack_order")
-        return buf, e
-    return _x3_cache(weight, (weight._version, weight.data_ptr(), weight.device, tuple(weight.shape)), make,
-                     kind="tile" if order == 0 else f"tile order {order}")
+        return _x3_packed(w, nbytes, lambda e, buf, st: native.lib().dvis_x3_tile_pack_order(
+            ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e, order, buf, st), "dvis_x3_tile_pack_order")
+    return _x3_cache(weight, [weight], make, kind="tile" if order == 0 else f"tile order {order}")
 
 
 # Row images (include/dvis_hip.h, "ROW IMAGES"; csrc/gemm_x3_tile.hip): the tiled GEMM's row operand pre-split by its producer.
@@ -1472,7 +1454,7 @@ def x3_ffn_ln(x, lin1, lin2, norm, pos=None, xexp=None, hexp=None):
                                                        N, e1, e2, ctypes.c_void_p(buf.data_ptr()),
                                                        native.stream_ptr(a.device)), "dvis_x3_ffn_pack")
         return buf, e1, e2
-    buf, e1, e2 = _x3_cache(w1, (w1._version, w2._version, w1.data_ptr(), w2.data_ptr(), w1.device), make, kind="ffn")
+    buf, e1, e2 = _x3_cache(w1, [w1, w2], make, kind="ffn")
     out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
     pos, pos_rows, out2 = _x3_pos(pos, x, N)
     with torch.cuda.device(x.device):
@@ -1631,14 +1613,8 @@ def conv1x1_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None):
     Co = weight.shape[0]
 
     def make():
-        w2 = weight.detach().reshape(Co, Ci).contiguous()
-        e = _x3_exp(w2)
-        buf = torch.empty(native.lib().dvis_conv1x1_x3_packed_bytes(Ci, Co), dtype=torch.uint8, device=w2.device)
-        with torch.cuda.device(w2.device):
-            native.check(native.lib().dvis_conv1x1_x3_pack(native.dev_ptr(w2, "weight"), Co, Ci, e, ctypes.c_void_p(buf.data_ptr()),
-                                                           native.stream_ptr(w2.device)), "dvis_conv1x1_x3_pack")
-        return buf, e
-    buf, wexp = _x3_cache(weight, (weight._version, weight.data_ptr(), weight.device), make, kind="conv1x1")
+        return _x3_pack_conv1x1(weight.detach().reshape(Co, Ci).contiguous())
+    buf, wexp = _x3_cache(weight, [weight], make, kind="conv1x1")
     OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
     out = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=x.device)
     step = _conv_x3_chunks(N, Ci, Co, H * W, OH * OW)
@@ -1678,18 +1654,12 @@ def conv1x1_x3_dual(a, w3, b3, x, ws, bs, relu=True, stride2=1, xexp=None):
 
     def make():
         wcat = torch.cat([w3.detach().reshape(Co, C), ws.detach().reshape(Co, C2)], 1).contiguous()
-        e = _x3_exp(wcat)
-        buf = torch.empty(native.lib().dvis_conv1x1_x3_packed_bytes(C + C2, Co), dtype=torch.uint8, device=wcat.device)
-        with torch.cuda.device(wcat.device):
-            native.check(native.lib().dvis_conv1x1_x3_pack(native.dev_ptr(wcat, "weight"), Co, C + C2, e, ctypes.c_void_p(buf.data_ptr()),
-                                                           native.stream_ptr(wcat.device)), "dvis_conv1x1_x3_pack")
+        buf, e = _x3_pack_conv1x1(wcat)
         bias = None
         if b3 is not None or bs is not None:
             bias = (0 if b3 is None else b3.detach()) + (0 if bs is None else bs.detach())
         return buf, e, bias
-    buf, wexp, bias = _x3_cache(w3, (w3._version, w3.data_ptr(), ws._version, ws.data_ptr(), w3.device,
-                                     None if b3 is None else b3._version, None if bs is None else bs._version), make,
-                                kind="conv1x1 + shortcut")
+    buf, wexp, bias = _x3_cache(w3, [w3, ws, b3, bs], make, kind="conv1x1 + shortcut")
     out = torch.empty((N, Co, H, W), dtype=torch.float32, device=a.device)
     step = min(_conv_x3_chunks(N, C, Co, H * W, H * W), _conv_x3_chunks(N, C2, Co, H2 * W2, H * W))
     with torch.cuda.device(a.device):
@@ -1714,14 +1684,8 @@ def conv3x3_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None):
     Co = weight.shape[0]
 
     def make():
-        w2 = weight.detach().contiguous()
-        e = _x3_exp(w2)
-        buf = torch.empty(native.lib().dvis_conv3x3_x3_packed_bytes(Ci, Co), dtype=torch.uint8, device=w2.device)
-        with torch.cuda.device(w2.device):
-            native.check(native.lib().dvis_conv3x3_x3_pack(native.dev_ptr(w2, "weight"), Co, Ci, e, ctypes.c_void_p(buf.data_ptr()),
-                                                           native.stream_ptr(w2.device)), "dvis_conv3x3_x3_pack")
-        return buf, e
-    buf, wexp = _x3_cache(weight, (weight._version, weight.data_ptr(), weight.device), make, kind="conv3x3")
+        return _x3_pack_conv3x3(weight.detach().contiguous())
+    buf, wexp = _x3_cache(weight, [weight], make, kind="conv3x3")
     OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
     out = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=x.device)
     step = _conv_x3_chunks(N, Ci, Co, H * W, OH * OW)
@@ -1757,10 +1721,11 @@ class OperandImage:
 
 
 def x3_images_ok(N, C, K, H, W, device, taps=1, stride=1):
-    """Operand images between two launches of csrc/conv1x1_x3.hip: split-f16 kernels on, a GPU, channel counts the image forms serve."""
+    """Operand images between two launches of csrc/conv1x1_x3.hip: split-f16 kernels on, a GPU, a 1x1 or 3x3 convolution (taps) of
+    channel counts the image forms serve."""
     if not (X3_IMAGES and x3_on() and device.type == "cuda" and not torch.is_grad_enabled()):
         return False
-    if C % 64 != 0 or not (K == 128 or K % 256 == 0) or N <= 0:
+    if taps not in (1, 9) or C % 64 != 0 or not (K == 128 or K % 256 == 0) or N <= 0:
         return False
     OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
     return bool(native.lib().dvis_conv1x1_x3_supported(C, K, 1, H * W, OH * OW))
@@ -1806,22 +1771,12 @@ def conv_x3_image(src, weight, bias=None, res=None, relu=False, stride=1, out_im
 
     def make():
         w2 = weight.detach().contiguous()
-        e = _x3_exp(w2)
-        nbytes = lib.dvis_conv1x1_x3_packed_bytes(C, K) * taps
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            if from_img:
-                native.check(lib.dvis_conv_x3_pack_image(native.dev_ptr(w2, "weight"), K, C, taps, e, ctypes.c_void_p(buf.data_ptr()),
-                                                         native.stream_ptr(dev)), "dvis_conv_x3_pack_image")
-            elif taps == 1:
-                native.check(lib.dvis_conv1x1_x3_pack(native.dev_ptr(w2.reshape(K, C), "weight"), K, C, e, ctypes.c_void_p(buf.data_ptr()),
-                                                      native.stream_ptr(dev)), "dvis_conv1x1_x3_pack")
-            else:
-                native.check(lib.dvis_conv3x3_x3_pack(native.dev_ptr(w2, "weight"), K, C, e, ctypes.c_void_p(buf.data_ptr()),
-                                                      native.stream_ptr(dev)), "dvis_conv3x3_x3_pack")
-        return buf, e
+        if from_img:
+            return _x3_packed(w2, lib.dvis_conv1x1_x3_packed_bytes(C, K) * taps, lambda e, buf, st: lib.dvis_conv_x3_pack_image(
+                native.dev_ptr(w2, "weight"), K, C, taps, e, buf, st), "dvis_conv_x3_pack_image")
+        return _x3_pack_conv1x1(w2.reshape(K, C)) if taps == 1 else _x3_pack_conv3x3(w2)
     kind = ("conv%dx%d" % ((1, 1) if taps == 1 else (3, 3))) + (" image-in" if from_img else "")
-    buf, wexp = _x3_cache(weight, (weight._version, weight.data_ptr(), weight.device), make, kind=kind)
+    buf, wexp = _x3_cache(weight, [weight], make, kind=kind)
     OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
     xe = src.exp if from_img else (X3_CONV_XEXP if xexp is None else xexp)
     oe = X3_CONV_XEXP if oexp is None else oexp
@@ -1874,15 +1829,7 @@ def bneck_stage_x3(x, blocks, xexp=None):
     def packed_conv1():
         w = blocks[0]["w1"]
 
-        def make():
-            w2d = w.detach().reshape(64, 64).contiguous()
-            e = _x3_exp(w2d)
-            buf = torch.empty(lib.dvis_conv1x1_x3_packed_bytes(64, 64), dtype=torch.uint8, device=dev)
-            with torch.cuda.device(dev):
-                native.check(lib.dvis_conv1x1_x3_pack(native.dev_ptr(w2d, "weight"), 64, 64, e, ctypes.c_void_p(buf.data_ptr()),
-                                                      native.stream_ptr(dev)), "dvis_conv1x1_x3_pack")
-            return buf, e
-        return _x3_cache(w, (w._version, w.data_ptr(), w.device), make, kind="conv1x1")
+        return _x3_cache(w, [w], lambda: _x3_pack_conv1x1(w.detach().reshape(64, 64).contiguous()), kind="conv1x1")
 
     def packed_block(i):
         b, nxt = blocks[i], (blocks[i + 1] if i + 1 < len(blocks) else None)
@@ -1904,9 +1851,8 @@ def bneck_stage_x3(x, blocks, xexp=None):
             b3 = b["b3"]
             if b["bs"] is not None:
                 b3 = b["bs"].detach() if b3 is None else b3.detach() + b["bs"].detach()
-            return buf, e2, e3, e1, (None if b3 is None else b3.detach().contiguous())
-        key = tuple((t._version, t.data_ptr()) if t is not None else None for t in (b["w2"], b["w3"], ws, w1n, b["b3"], b["bs"])) + (dev,)
-        return _x3_cache(b["w2"], key, make, kind="bottleneck chain")
+            return buf, e2, e3, e1, (None if b3 is None else b3.detach().clone())      # (an own tensor, derived.py)
+        return _x3_cache(b["w2"], [b["w2"], b["w3"], ws, w1n, b["b3"], b["bs"]], make, kind="bottleneck chain")
 
     img_bytes = lib.dvis_bneck_x3_image_bytes(N, H, W)
     imgs = [torch.empty(img_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -1938,8 +1884,19 @@ def bneck_stage_x3(x, blocks, xexp=None):
     return ys[(len(blocks) - 1) % 2]
 
 
+def _fp32_pack(weight, kind, numel, pack, name):
+    """The fp32 kernels' transformed weights (`numel` floats through `pack(weight pointer, buffer pointer, stream)`), one per
+    (weight, kind) in derived.TABLE."""
+    def make():
+        w = weight.detach().contiguous()
+        uf = torch.empty(numel, dtype=torch.float32, device=w.device)
+        with torch.cuda.device(w.device):
+            native.check(pack(native.dev_ptr(w, "weight"), native.dev_ptr(uf, "uf"), native.stream_ptr(w.device)), name)
+        return uf
+    return derived.TABLE.get(weight, kind, [weight], make)
+
+
 CONV1X1_MFMA = os.environ.get("DVIS_CONV1X1_MFMA", "1") != "0"
-_C1_PACKED = {}
 
 
 def conv1x1s2_supported(x, weight):
@@ -1956,22 +1913,13 @@ def conv1x1_mfma(x, weight, bias=None, res=None, relu=False, stride=1):
     stride=2: the same on x[:, :, ::2, ::2] (read in place)."""
     N, Ci, H, W = x.shape
     Co = weight.shape[0]
-    key = (weight._version, weight.data_ptr(), weight.device)
-    ent = _C1_PACKED.get(id(weight))
-    if ent is None or ent[0] != key:
-        w2 = weight.detach().reshape(Co, Ci).contiguous()
-        uf = ent[1] if ent is not None and ent[1].device == w2.device and ent[1].numel() == Co * Ci else torch.empty_like(w2)
-        with torch.cuda.device(w2.device):
-            native.check(native.lib().dvis_conv1x1_mfma_pack(native.dev_ptr(w2, "weight"), native.dev_ptr(uf, "uf"), Co, Ci,
-                                                             native.stream_ptr(w2.device)), "dvis_conv1x1_mfma_pack")
-        if len(_C1_PACKED) > 512:
-            _C1_PACKED.clear()
-        _C1_PACKED[id(weight)] = ent = (key, uf, weight)
+    uf = _fp32_pack(weight, "conv1x1 mfma", Co * Ci, lambda w, uf, st: native.lib().dvis_conv1x1_mfma_pack(w, uf, Co, Ci, st),
+                    "dvis_conv1x1_mfma_pack")
     if stride == 2:
         out = torch.empty((N, Co, (H + 1) // 2, (W + 1) // 2), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
             rc = native.lib().dvis_conv1x1s2_mfma(
-                native.dev_ptr(x, "x"), native.dev_ptr(ent[1], "uf"), None if bias is None else native.dev_ptr(bias.detach(), "bias"),
+                native.dev_ptr(x, "x"), native.dev_ptr(uf, "uf"), None if bias is None else native.dev_ptr(bias.detach(), "bias"),
                 None if res is None else native.dev_ptr(res, "res"), native.dev_ptr(out, "out"), N, Ci, Co, H, W, 1 if relu else 0,
                 native.stream_ptr(x.device))
         native.check(rc, "dvis_conv1x1s2_mfma")
@@ -1979,7 +1927,7 @@ def conv1x1_mfma(x, weight, bias=None, res=None, relu=False, stride=1):
     out = torch.empty((N, Co, H, W), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         rc = native.lib().dvis_conv1x1_mfma(
-            native.dev_ptr(x, "x"), native.dev_ptr(ent[1], "uf"), None if bias is None else native.dev_ptr(bias.detach(), "bias"),
+            native.dev_ptr(x, "x"), native.dev_ptr(uf, "uf"), None if bias is None else native.dev_ptr(bias.detach(), "bias"),
             None if res is None else native.dev_ptr(res, "res"), native.dev_ptr(out, "out"), N, Ci, Co, H * W, 1 if relu else 0,
             native.stream_ptr(x.device))
     native.check(rc, "dvis_conv1x1_mfma")
@@ -1987,45 +1935,21 @@ def conv1x1_mfma(x, weight, bias=None, res=None, relu=False, stride=1):
 
 
 WINOGRAD_DEFAULT = os.environ.get("DVIS_WINOGRAD", "1") != "0"
-_WINOGRAD_PACKED = {}     # id(weight) -> ((version, data_ptr, device), packed): transformed weights, made once per weight
 
 
 def _winograd_weights(weight):
-    key = (weight._version, weight.data_ptr(), weight.device)
-    ent = _WINOGRAD_PACKED.get(id(weight))
-    if ent is None or ent[0] != key:
-        K, C = weight.shape[:2]
-        w = weight.detach().contiguous()
-        uf = ent[1] if ent is not None and ent[1].device == w.device and ent[1].numel() == 16 * K * C else \
-            torch.empty(16 * K * C, dtype=torch.float32, device=w.device)       # refreshed in place (captured graphs)
-        with torch.cuda.device(w.device):
-            native.check(native.lib().dvis_conv3x3_winograd_pack(native.dev_ptr(w, "weight"), native.dev_ptr(uf, "uf"), K, C,
-                                                                 native.stream_ptr(w.device)), "dvis_conv3x3_winograd_pack")
-        if len(_WINOGRAD_PACKED) > 512:       # (weights that were replaced, e.g. re-folded FrozenBN: drop their packs)
-            _WINOGRAD_PACKED.clear()
-        _WINOGRAD_PACKED[id(weight)] = ent = (key, uf, weight)     # (holds the weight: id() stays unique)
-    return ent[1]
+    K, C = weight.shape[:2]
+    return _fp32_pack(weight, "winograd", 16 * K * C, lambda w, uf, st: native.lib().dvis_conv3x3_winograd_pack(w, uf, K, C, st),
+                      "dvis_conv3x3_winograd_pack")
 
 
-_S2_PACKED = {}
 S2_DEFAULT = os.environ.get("DVIS_CONV3X3S2", "1") != "0"
 
 
 def _s2_weights(weight):
-    key = (weight._version, weight.data_ptr(), weight.device)
-    ent = _S2_PACKED.get(id(weight))
-    if ent is None or ent[0] != key:
-        K, C = weight.shape[:2]
-        w = weight.detach().contiguous()
-        uf = ent[1] if ent is not None and ent[1].device == w.device and ent[1].numel() == 12 * K * C else \
-            torch.empty(12 * K * C, dtype=torch.float32, device=w.device)
-        with torch.cuda.device(w.device):
-            native.check(native.lib().dvis_conv3x3s2_pack(native.dev_ptr(w, "weight"), native.dev_ptr(uf, "uf"), K, C,
-                                                          native.stream_ptr(w.device)), "dvis_conv3x3s2_pack")
-        if len(_S2_PACKED) > 512:
-            _S2_PACKED.clear()
-        _S2_PACKED[id(weight)] = ent = (key, uf, weight)
-    return ent[1]
+    K, C = weight.shape[:2]
+    return _fp32_pack(weight, "conv3x3s2", 12 * K * C, lambda w, uf, st: native.lib().dvis_conv3x3s2_pack(w, uf, K, C, st),
+                      "dvis_conv3x3s2_pack")
 
 
 def conv3x3s2_bias_act(x, weight, bias=None, relu=False, own=None):
@@ -2058,9 +1982,6 @@ def conv3x3s2_bias_act(x, weight, bias=None, relu=False, own=None):
     return bias_act_(y, None if bias is None else bias.detach(), None, relu)
 
 
-_STEM_PACKED = {}
-
-
 def conv7x7s2_stem(x, weight, bias=None, relu=False, own=None):
     """relu?(conv2d(x (N, 3, H, W), weight (64, 3, 7, 7), stride 2, padding 3) + bias[k]): the ResNet stem convolution on the
     direct fp32-MFMA kernel (csrc/conv7x7s2.hip) where the shape is served (own=True: raise otherwise), else the library."""
@@ -2072,21 +1993,11 @@ def conv7x7s2_stem(x, weight, bias=None, relu=False, own=None):
     if own and not ok:
         raise RuntimeError(f"conv7x7s2_stem(own=True): C={C} K={K} H={H} W={W} is not served (dvis_conv7x7s2_supported)")
     if ok and (own or (own is None and WINOGRAD_DEFAULT and S2_DEFAULT)):
-        key = (weight._version, weight.data_ptr(), weight.device)
-        ent = _STEM_PACKED.get(id(weight))
-        if ent is None or ent[0] != key:
-            w = weight.detach().contiguous()
-            uf = ent[1] if ent is not None and ent[1].device == w.device else torch.empty(10240, dtype=torch.float32, device=w.device)
-            with torch.cuda.device(w.device):
-                native.check(native.lib().dvis_conv7x7s2_pack(native.dev_ptr(w, "weight"), native.dev_ptr(uf, "uf"),
-                                                              native.stream_ptr(w.device)), "dvis_conv7x7s2_pack")
-            if len(_STEM_PACKED) > 64:
-                _STEM_PACKED.clear()
-            _STEM_PACKED[id(weight)] = ent = (key, uf, weight)
+        uf = _fp32_pack(weight, "conv7x7s2", 10240, native.lib().dvis_conv7x7s2_pack, "dvis_conv7x7s2_pack")
         x = x if x.is_contiguous() else x.contiguous()
         out = torch.empty((N, 64, H // 2, W // 2), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            rc = native.lib().dvis_conv7x7s2(native.dev_ptr(x, "x"), native.dev_ptr(ent[1], "uf"),
+            rc = native.lib().dvis_conv7x7s2(native.dev_ptr(x, "x"), native.dev_ptr(uf, "uf"),
                                              None if bias is None else native.dev_ptr(bias.detach(), "bias"),
                                              native.dev_ptr(out, "out"), N, H, W, 1 if relu else 0, native.stream_ptr(x.device))
         native.check(rc, "dvis_conv7x7s2")

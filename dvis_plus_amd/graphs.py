@@ -11,6 +11,8 @@ import collections
 
 import torch
 
+from . import derived
+
 
 class GraphRunner:
     """max_entries bounds the cache (least recently used graph dropped first): every distinct clip length costs two
@@ -69,8 +71,7 @@ class FusedKV:
         8 l + h of ONE attention call over layers x heads (the tracker's per-frame cross-attentions, tracker.py:293-318);
         "q" = the Q rows [0, C) (all layers' queries of ONE input: the tracker's per-frame reference, tracker.py:278);
         "out" = the out_proj weights stacked (layers, C, C) / biases (layers, C) — one batched GEMM (dvis_gemm_nt_bb)."""
-        self._key, self._W, self._b = None, None, None
-        self._rows = rows
+        self._rows, self._cat = rows, derived.Derived()
 
     def get(self, layers, C):
         if self._rows == "out":
@@ -79,26 +80,15 @@ class FusedKV:
         else:
             ws = [l.multihead_attn.in_proj_weight for l in layers]
             bs = [l.multihead_attn.in_proj_bias for l in layers]
-        ver = tuple(t._version for t in ws + bs) + tuple(t.data_ptr() for t in ws + bs)
-        dev = ws[0].device
-        sl = slice(C, None) if self._rows == "kv" else slice(0, C)
-        if self._key != (ver, dev):
+
+        def make():
             if self._rows == "out":
-                W = torch.stack([w.detach() for w in ws], 0)
-                b = torch.stack([x.detach() for x in bs], 0)
-            elif self._rows == "k_v":
-                W = torch.cat([w[C:2 * C].detach() for w in ws] + [w[2 * C:].detach() for w in ws], 0)
-                b = torch.cat([x[C:2 * C].detach() for x in bs] + [x[2 * C:].detach() for x in bs], 0)
-            else:
-                W = torch.cat([w[sl].detach() for w in ws], 0)
-                b = torch.cat([x[sl].detach() for x in bs], 0)
-            if self._W is not None and self._W.device == dev and self._W.shape == W.shape and self._W.dtype == W.dtype:
-                self._W.copy_(W)
-                self._b.copy_(b)
-            else:
-                self._W, self._b = W.contiguous(), b.contiguous()
-            self._key = (ver, dev)
-        return self._W, self._b
+                return tuple(torch.stack([t.detach() for t in ts], 0) for ts in (ws, bs))
+            if self._rows == "k_v":
+                return tuple(torch.cat([t[C:2 * C].detach() for t in ts] + [t[2 * C:].detach() for t in ts], 0) for ts in (ws, bs))
+            sl = slice(C, None) if self._rows == "kv" else slice(0, C)
+            return tuple(torch.cat([t[sl].detach() for t in ts], 0) for ts in (ws, bs))
+        return self._cat.get(ws + bs, make)
 
 
 class ConvAsGemm:
@@ -106,17 +96,6 @@ class ConvAsGemm:
     cached per module and — like FusedKV — refreshed IN PLACE when the parameter changes, because captured hipGraphs
     point at the cached tensor."""
 
-    def __init__(self):
-        self._cache = {}
-
     def get(self, conv):
         w = conv.weight
-        key = (w._version, w.data_ptr(), w.device)
-        ent = self._cache.get(id(conv))
-        if ent is None or ent[0] != key:
-            W = w.detach().permute(0, 2, 1).reshape(w.shape[0], -1).contiguous()
-            if ent is not None and ent[1].device == W.device and ent[1].shape == W.shape:
-                ent[1].copy_(W)
-                W = ent[1]
-            self._cache[id(conv)] = ent = (key, W)
-        return ent[1]
+        return derived.TABLE.get(conv, "conv1d as gemm", [w], lambda: w.detach().permute(0, 2, 1).reshape(w.shape[0], -1).clone(memory_format=torch.contiguous_format))

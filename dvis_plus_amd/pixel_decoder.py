@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.init import constant_, normal_, xavier_uniform_
 
-from . import functions as Fn
+from . import derived, functions as Fn
 from .d2 import configurable
 from .registry import SEM_SEG_HEADS_REGISTRY, ShapeSpec
 
@@ -99,7 +99,7 @@ class MSDeformAttn(nn.Module):
         self.attention_weights = nn.Linear(d_model, n_heads * n_levels * n_points)
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
-        self._fused = None               # (version key, W_cat, b_cat) for the inference fast path
+        self._fused = derived.Derived()  # (W_cat, b_cat, head_stride, the two without zero rows) for the inference fast path
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -122,13 +122,13 @@ class MSDeformAttn(nn.Module):
                 proj.bias.zero_()
 
     def _fused_projection(self):
-        """-> (weight, bias, head_stride) of the ONE GEMM that produces offsets and logits.  head_stride 0: rows in the
+        """-> (weight, bias, head_stride, weight / bias without the zero rows) of the ONE GEMM that produces offsets and logits.  head_stride 0: rows in the
         reference's order [all offsets | all logits | zero rows up to a multiple of 64]; head_stride s: per-head slots
         [head m: 2LP offset rows | LP logit rows | zero rows] of s = (padded width) / M output columns — the same GEMM
         width (8 heads x 36 = 288 -> 320 = 8 x 40), but a (query, head) pair's parameters are one contiguous 160-byte run."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (so.weight._version, so.bias._version, aw.weight._version, aw.bias._version, so.weight.device, _MSDA_SLOTS)
-        if self._fused is None or self._fused[0] != key:
+
+        def make():
             M, LP = self.n_heads, self.n_levels * self.n_points
             width = -(-(3 * M * LP) // 64) * 64
             # zero rows up to a multiple of 64 output columns: the library's GEMM for (579 600 x 256) x (256 x 288) runs
@@ -152,9 +152,9 @@ class MSDeformAttn(nn.Module):
                     w = torch.cat([w, w.new_zeros(pad, w.shape[1])], 0)
                     b = torch.cat([b, b.new_zeros(pad)], 0)
             w, b = w.contiguous(), b.contiguous()
-            rows = w.shape[0] if slot else 3 * self.n_heads * self.n_levels * self.n_points
-            self._fused = (key, w, b, slot, w[:rows], b[:rows])     # [4:]: without the zero rows (csrc/gemm_x3.hip needs none)
-        return self._fused[1], self._fused[2], self._fused[3]
+            rows = w.shape[0] if slot else 3 * M * LP
+            return w, b, slot, w[:rows], b[:rows]       # [3:]: without the zero rows (csrc/gemm_x3.hip needs none)
+        return self._fused.get([so.weight, so.bias, aw.weight, aw.bias], make, (_MSDA_SLOTS,))
 
     def _fast_path_ok(self, query, reference_points, input_padding_mask):
         d = self.d_model // self.n_heads
@@ -211,7 +211,7 @@ class MSDeformAttn(nn.Module):
                 value = value.masked_fill(input_padding_mask[..., None], float(0))
             value = value.view(N, Len_in, M, self.d_model // M)
         if fast:
-            w, b, slot = self._fused_projection()
+            w, b, slot, w_rows, b_rows = self._fused_projection()
             # where a row's offsets / logits start (slots: inside the head's slot)
             o_off, l_off = ((L * P, 0) if _MSDA_SLOTS == 2 else (0, 2 * L * P)) if slot else (0, M * L * P * 2)
             po = pl = None
@@ -225,9 +225,9 @@ class MSDeformAttn(nn.Module):
                 query_pos = None
             if x3 and query_pos is not None and po is None:
                 # `with_pos_embed(src, pos)` inside the projection kernel: the (N, Lq, C) sum is never written
-                proj = Fn.x3_linear(query, self._fused[4], self._fused[5], xadd=query_pos).view(N * Len_q, -1)
+                proj = Fn.x3_linear(query, w_rows, b_rows, xadd=query_pos).view(N * Len_q, -1)
             elif x3:
-                proj = Fn.x3_linear(query.reshape(N * Len_q, self.d_model), self._fused[4], self._fused[5])
+                proj = Fn.x3_linear(query.reshape(N * Len_q, self.d_model), w_rows, b_rows)
             else:
                 proj = Fn.linear(query.reshape(N * Len_q, self.d_model), w, b, tall=True)     # offsets | logits in one GEMM
             ref = reference_points if reference_points.is_contiguous() else reference_points.contiguous()

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import functions as Fn
+from . import derived, functions as Fn
 from .pixel_decoder import ConvNorm, PositionEmbeddingSine, c2_xavier_fill
 from .d2 import configurable
 from .registry import TRANSFORMER_DECODER_REGISTRY
@@ -171,7 +171,7 @@ class _MaskedDecoderBase(nn.Module):
                 self.input_proj.append(nn.Sequential())
         self.class_embed = nn.Linear(hidden_dim, num_classes + 1)
         self.mask_embed = MLP(hidden_dim, hidden_dim, mask_dim, 3)
-        self._kv_cache = None
+        self._kv_cache = derived.Derived()
         self.debug_masks = None      # tests: a list here receives every layer's effective attention mask (N, Q, hw) bool
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys,
@@ -197,11 +197,7 @@ class _MaskedDecoderBase(nn.Module):
 
     # ---- K / V projection weights of all layers reading level l, concatenated once
     def _level_kv_weights(self):
-        ver = tuple(t._version for l in self.transformer_cross_attention_layers
-                    for t in (l.multihead_attn.in_proj_weight, l.multihead_attn.in_proj_bias)) \
-            + (self.level_embed.weight._version,)
-        dev = self.decoder_norm.weight.device
-        if self._kv_cache is None or self._kv_cache[0] != (ver, dev):
+        def make():
             per_level = []
             for lvl in range(self.num_feature_levels):
                 idx = [i for i in range(self.num_layers) if i % self.num_feature_levels == lvl]
@@ -212,10 +208,12 @@ class _MaskedDecoderBase(nn.Module):
                 Wv, bv = torch.cat([w[2] for w in ws], 0).detach(), torch.cat([w[3] for w in ws], 0).detach()
                 # V = (tok + level_embed) Wv^T + bv = tok Wv^T + (bv + Wv level_embed): the folded bias, made once per weights
                 bv_le = (bv.double() + Wv.double() @ self.level_embed.weight[lvl].detach().double()).float()
-                per_level.append((idx, torch.cat([w[0] for w in ws], 0).detach(), torch.cat([w[1] for w in ws], 0).detach(),
+                per_level.append((tuple(idx), torch.cat([w[0] for w in ws], 0).detach(), torch.cat([w[1] for w in ws], 0).detach(),
                                   Wv, bv, bv_le))
-            self._kv_cache = ((ver, dev), per_level)
-        return self._kv_cache[1]
+            return tuple(per_level)
+        return self._kv_cache.get([t for l in self.transformer_cross_attention_layers
+                                   for t in (l.multihead_attn.in_proj_weight, l.multihead_attn.in_proj_bias)]
+                                  + [self.level_embed.weight], make)
 
     @staticmethod
     def _f32_inputs(x, mask_features):

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import functions as Fn
+from . import derived, functions as Fn
 from .pixel_decoder import MSDeformAttn
 from .registry import BACKBONE_REGISTRY, ShapeSpec
 
@@ -36,15 +36,13 @@ class PatchEmbed(nn.Module):
         self.img_size, self.patch_size = (img_size, img_size), (patch_size, patch_size)
         self.num_patches = (img_size // patch_size) ** 2
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
+        self._flat = derived.Derived()
 
     def _flat_weight(self):
         """The stride-p p x p convolution as a linear layer over flattened patches: (D, 3 p p), an own tensor (not a view: the
         packed split-f16 image is cached per weight tensor), refreshed when the parameter changes."""
         w = self.proj.weight
-        key = (w._version, w.data_ptr(), w.device)
-        if getattr(self, "_flat", None) is None or self._flat[0] != key:
-            self._flat = (key, w.detach().reshape(w.shape[0], -1).clone())
-        return self._flat[1]
+        return self._flat.get([w], lambda: w.detach().reshape(w.shape[0], -1).clone())
 
     def forward(self, x, return_HW=False):
         B, Cin, H, W = x.shape
@@ -77,19 +75,17 @@ class _Folded:
     """out-projection with the LayerScale gamma that follows it folded in: gamma * (W a + b) = (gamma W) a + gamma b."""
 
     def __init__(self):
-        self._cache = None
+        self._cache = derived.Derived()
 
     def get(self, lin, ls):
         g = ls.gamma if isinstance(ls, LayerScale) else None
-        key = (lin.weight._version, lin.bias._version if lin.bias is not None else -1,
-               g._version if g is not None else -1, lin.weight.device)
-        if self._cache is None or self._cache[0] != key:
+
+        def make():
             w, b = lin.weight.detach(), None if lin.bias is None else lin.bias.detach()
-            if g is not None:
-                w = w * g.detach()[:, None]
-                b = None if b is None else b * g.detach()
-            self._cache = (key, w.contiguous(), b)
-        return self._cache[1], self._cache[2]
+            if g is None:       # (own tensors, derived.py)
+                return w.clone(), None if b is None else b.clone()
+            return (w * g.detach()[:, None]).contiguous(), None if b is None else b * g.detach()
+        return self._cache.get([lin.weight, lin.bias, g], make)
 
 
 class Attention(nn.Module):
@@ -194,15 +190,14 @@ class DinoVisionTransformer(nn.Module):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
-        self._pos_cache = {}
+        self._pos_cache = derived.Derived()
 
     def interpolate_pos_encoding(self, npatch, w, h):
         """backbones.py:176-202; (w, h) are the image height / width as the reference names them.  Cached per size."""
         N = self.pos_embed.shape[1] - 1
         if npatch == N and w == h:
             return self.pos_embed
-        key = (w, h, self.pos_embed._version, self.pos_embed.device)
-        if key not in self._pos_cache:
+        def make():
             pe = self.pos_embed.detach().float()
             dim = pe.shape[-1]
             w0, h0 = w // self.patch_size + 0.1, h // self.patch_size + 0.1
@@ -210,8 +205,8 @@ class DinoVisionTransformer(nn.Module):
             pp = F.interpolate(pe[:, 1:].reshape(1, s, s, dim).permute(0, 3, 1, 2),
                                scale_factor=(w0 / math.sqrt(N), h0 / math.sqrt(N)), mode="bicubic")
             assert int(w0) == pp.shape[-2] and int(h0) == pp.shape[-1]
-            self._pos_cache = {key: torch.cat((pe[:, :1], pp.permute(0, 2, 3, 1).reshape(1, -1, dim)), dim=1)}
-        return self._pos_cache[key]
+            return torch.cat((pe[:, :1], pp.permute(0, 2, 3, 1).reshape(1, -1, dim)), dim=1)
+        return self._pos_cache.get([self.pos_embed], make, (w, h))
 
     def prepare_tokens_with_masks(self, x, masks=None, return_HW=False):
         assert masks is None, "masked tokens are a DINOv2 pre-training feature, unused by the adapter"
@@ -366,11 +361,7 @@ class SpatialPriorModule(nn.Module):
         """(weight, bias) of `conv` with the eval-mode BatchNorm that follows folded in (y = s (W x) + (beta - mean s), s = gamma /
         sqrt(var + eps)), cached per parameter version.  embed7: the 3 x 3 / stride 2 / padding 1 kernel laid into the centre of a
         7 x 7 / padding 3 one (the same convolution) — the shape the direct stem kernel serves (csrc/conv7x7s2.hip)."""
-        key = (conv.weight._version, bn.weight._version, bn.bias._version, bn.running_mean._version, bn.running_var._version,
-               conv.weight.device, embed7)
-        cache = self.__dict__.setdefault("_fold_cache", {})
-        ent = cache.get(id(conv))
-        if ent is None or ent[0] != key:
+        def make():
             with torch.no_grad():
                 s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
                 w = (conv.weight.double() * s.view(-1, 1, 1, 1)).float()
@@ -379,8 +370,9 @@ class SpatialPriorModule(nn.Module):
                     w7 = w.new_zeros(w.shape[0], w.shape[1], 7, 7)
                     w7[:, :, 2:5, 2:5] = w
                     w = w7
-                cache[id(conv)] = ent = (key, w.contiguous(), b)
-        return ent[1], ent[2]
+                return w.contiguous(), b
+        return derived.TABLE.get(conv, "BatchNorm folded", [conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var], make,
+                                 (embed7,))
 
     def own_ok(self, x):
         bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
@@ -532,14 +524,11 @@ class DinoV2ViTAdapter(nn.Module):
 
     def _bn_affine(self, bn):
         """Eval-mode BatchNorm as (scale, shift) per channel, fp64 arithmetic rounded once, cached per parameter version."""
-        key = tuple(p._version for p in (bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (bn.weight.device,)
-        cache = self.__dict__.setdefault("_bn_cache", {})
-        ent = cache.get(id(bn))
-        if ent is None or ent[0] != key:
+        def make():
             with torch.no_grad():
                 s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-                cache[id(bn)] = ent = (key, s.float().contiguous(), (bn.bias.double() - bn.running_mean.double() * s).float().contiguous())
-        return ent[1], ent[2]
+                return s.float().contiguous(), (bn.bias.double() - bn.running_mean.double() * s).float().contiguous()
+        return derived.TABLE.get(bn, "BatchNorm affine", [bn.weight, bn.bias, bn.running_mean, bn.running_var], make)
 
     def _res2_fused_ok(self, c1, t):
         bn = self.norm1
@@ -553,15 +542,16 @@ class DinoV2ViTAdapter(nn.Module):
         with norm1's eval affine folded in: W_l[(dy, dx, co), ci] = s[co] * up.weight[ci, co, dy, dx]; shift = s * up.bias + beta -
         mean * s.  Cached per parameter version."""
         up, bn = self.up, self.norm1
-        key = tuple(p._version for p in (up.weight, up.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)) + (up.weight.device,)
-        if getattr(self, "_res2_cache", None) is None or self._res2_cache[0] != key:
+
+        def make():
             with torch.no_grad():
                 s = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
                 sh = s * up.bias.double() + bn.bias.double() - bn.running_mean.double() * s
                 C = up.weight.shape[1]
                 w_l = (up.weight.double() * s.view(1, C, 1, 1)).permute(2, 3, 1, 0).reshape(4 * C, up.weight.shape[0])
-                self._res2_cache = (key, w_l.float().contiguous(), s.float().contiguous(), sh.float().contiguous())
-        return self._res2_cache[1:]
+                return w_l.float().contiguous(), s.float().contiguous(), sh.float().contiguous()
+        return derived.TABLE.get(up, "ConvTranspose2d + BatchNorm as linear",
+                                 [up.weight, up.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var], make)
 
 
 def get_adapter_args(name="vitl"):

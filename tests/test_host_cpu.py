@@ -189,28 +189,33 @@ def test_x3_stage_switches_and_pack_cache():
         assert not Fn.x3_on()
     finally:
         Fn.X3, Fn.X3_OFF = old_x3, old_off
-    # least-recently-used eviction, one entry per (weight, kind), re-made when the version key changes
-    cache = Fn._PackCache(cap=3)
+    # least-recently-used eviction, one entry per (weight, kind), re-made when the weight's fingerprint changes
+    from dvis_plus_amd import derived
+    cache = derived.Table(cap=3)
     made = []
     import unittest.mock as mock
     ws = [torch.zeros(2, 2) for _ in range(5)]
-    with mock.patch.object(Fn.X3_GUARD, "word", lambda dev: None), mock.patch.object(Fn.native, "lib") as lib:
+    with mock.patch.object(Fn.X3_GUARD, "word", lambda dev: None), mock.patch.object(Fn.native, "lib") as lib, \
+            mock.patch.object(derived, "TABLE", cache):
         lib.return_value.dvis_x3_set_tag = lambda t: 1
-        get = lambda w, kind, ver: cache.get(w, kind, ver, lambda: made.append((id(w), kind, ver)) or (id(w), kind))
-        get(ws[0], "linear", 0), get(ws[0], "ffn", 0), get(ws[1], "linear", 0)
+        get = lambda w, kind: Fn._x3_cache(w, [w], lambda: made.append((id(w), kind)) or (id(w), kind), kind)
+        get(ws[0], "linear"), get(ws[0], "ffn"), get(ws[1], "linear")
         assert len(cache) == 3 and len(made) == 3
-        get(ws[0], "linear", 0)                       # hit: refreshed, nothing made
+        get(ws[0], "linear")                          # hit: refreshed, nothing made
         assert len(made) == 3
-        get(ws[2], "linear", 0)                       # evicts the least recently used: (ws[0], "ffn")
-        assert len(cache) == 3 and len(made) == 4
-        get(ws[0], "linear", 0)
+        get(ws[2], "linear")                          # evicts the least recently used: (ws[0], "ffn")
+        assert len(cache) == 3 and len(made) == 4 and (id(ws[0]), "ffn") not in cache.d
+        get(ws[0], "linear")
         assert len(made) == 4                         # ... not the one just used
-        get(ws[0], "ffn", 0)
+        get(ws[0], "ffn")
         assert len(made) == 5                         # the evicted one is re-made
-        get(ws[0], "ffn", 1)
+        tag = cache.d[(id(ws[0]), "ffn")].note
+        ws[0].add_(1.0)
+        get(ws[0], "ffn")
         assert len(made) == 6                         # a new weight version re-packs in place
-        tags = {e[3] for e in cache.d.values()}
-        assert len(tags) == len(cache.d)              # every packed weight has its own range-guard tag
+        assert cache.d[(id(ws[0]), "ffn")].note == tag        # ... under the same range-guard tag
+        tags = {e.note for e in cache.d.values()}
+        assert len(tags) == len(cache.d) and None not in tags         # every packed weight has its own range-guard tag
 
 
 def test_range_guard_names_the_layer():

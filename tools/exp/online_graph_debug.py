@@ -30,9 +30,10 @@ with torch.no_grad():
     pred = m.sem_seg_head.predictor
     def state():
         kv = pred._kv_cache
-        ptrs = [t.data_ptr() for lvl in kv[1] if lvl is not None for t in lvl[1:]]
-        packs = {k: (v[1][0].data_ptr(), v[3]) for k, v in __import__("dvis_plus_amd.functions", fromlist=["x"])._X3_PACKED.d.items()}
-        return kv[0], ptrs, packs
+        ptrs = [t.data_ptr() for lvl in kv.value if lvl is not None for t in lvl[1:]]
+        packs = {k: (v.value[0].data_ptr(), v.note) for k, v in __import__("dvis_plus_amd.derived", fromlist=["x"]).TABLE.d.items()
+                 if v.note is not None}
+        return kv.key, ptrs, packs
     s0 = state()
     # whole forward
     v = {"image": frames, "height": 360, "width": 640}
