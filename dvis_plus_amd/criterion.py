@@ -146,6 +146,39 @@ class SetCriterion(VideoSetCriterion):
         return super().forward(outputs, targets)
 
 
+def reference_contrastive_loss(references, match_result):
+    """DVIS_Plus_online.get_cl_loss_ref + loss_reid (dvis_Plus/meta_architecture.py:981-1065, dvis_Plus/utils.py:51-94) in one
+    batched form.  references (T, Q, C): the tracker's "pred_references", one row of queries per frame; match_result[t] = (query
+    rows, target rows) of frame t.  Every matched query r of a frame t >= 1 is an anchor, once against frame t - 1 and, where
+    there is one, once against frame t + 1: row r of that frame is its positive, the other Q - 1 rows are negatives.
+    loss_reid = mean over the items of log(1 + sum_neg exp(neg . anchor - pos . anchor)); loss_aux_reid = mean over the items of
+    mean_q (cos(row q, anchor) - [q == r])^2.  No item: both are 0 with a graph to `references`."""
+    T, Q, _ = references.shape
+    anchor_t, other_t, rows = [], [], []
+    for t in range(1, T):
+        src, tgt = match_result[t]
+        by_target = {}
+        for r, g in zip(src.tolist(), tgt.tolist()):
+            by_target[g] = r
+        for r in by_target.values():
+            for o in (t - 1, t + 1):
+                if o < T:
+                    anchor_t.append(t), other_t.append(o), rows.append(r)
+    if not rows:
+        zero = references.sum() * 0
+        return {"loss_reid": zero, "loss_aux_reid": zero}
+    dev = references.device
+    rows = torch.tensor(rows, device=dev)
+    anchor = references[torch.tensor(anchor_t, device=dev), rows]                  # (n, C)
+    other = references[torch.tensor(other_t, device=dev)]                          # (n, Q, C)
+    dot = torch.einsum("nqc,nc->nq", other, anchor)
+    # the positive's own entry is exactly 0: the "1 +" of the formula
+    reid = torch.logsumexp(dot - dot.gather(1, rows[:, None]), dim=1).mean()
+    cos = torch.einsum("nqc,nc->nq", F.normalize(other, dim=2), F.normalize(anchor, dim=1))
+    aux = (cos - F.one_hot(rows, Q).to(cos.dtype)).square().mean()
+    return {"loss_reid": reid, "loss_aux_reid": aux}
+
+
 def build_criterion(cfg, meta_arch=None):
     """The criterion the reference's ``from_config`` of `meta_arch` builds (MODEL.META_ARCHITECTURE when None): "MinVIS"
     (dvis_Plus/meta_architecture.py:105-138), "DVIS_Plus_online" (:516-571), "DVIS_Plus_offline" (:1175-1243), "MaskFormer"

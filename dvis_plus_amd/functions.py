@@ -269,15 +269,9 @@ def _f32_gpu(t, name):
     return native.dev_ptr(t, name)
 
 
-def mask_logits(mask_embed, mask_features):
-    """einsum("bqc,bchw->bqhw") of forward_prediction_heads
-    (dvis_Plus/video_mask2former_transformer_decoder.py:363), exact-fp32 MFMA.  (B,Q,C) x (B,C,H,W) -> (B,Q,H,W)."""
+def _mask_logits_kernel(mask_embed, mask_features):
     B, Q, C = mask_embed.shape
-    Bf, Cf, H, W = mask_features.shape
-    if (Bf, Cf) != (B, C):
-        raise RuntimeError("mask_logits: mask_embed (B,Q,C) and mask_features (B,C,H,W) disagree")
-    if _on_cpu(mask_embed, mask_features):
-        return cpu_ops.mask_logits(mask_embed, mask_features)
+    H, W = mask_features.shape[-2:]
     pe, pf = _f32_gpu(mask_embed, "mask_embed"), _f32_gpu(mask_features, "mask_features")
     out = torch.empty((B, Q, H, W), dtype=torch.float32, device=mask_embed.device)
     with torch.cuda.device(mask_embed.device):
@@ -285,6 +279,139 @@ def mask_logits(mask_embed, mask_features):
                                            native.stream_ptr(mask_embed.device))
     native.check(rc, "dvis_mask_logits")
     return out
+
+
+def mask_logits_backward(grad_logits, mask_features):
+    """Backward of ``mask_logits`` with respect to ``mask_embed`` (csrc/mask_gemm_backward.hip): grad_logits (B, R, H, W) and
+    mask_features (B, C, H, W), contiguous float32 GPU tensors -> (grad_embed (B, R, C) = einsum("brp,bcp->brc"), row_sum (B, R) =
+    grad_logits summed over the pixels).  Exact fp32, and the same bits on every call: the pixels are cut into slabs by their
+    number alone and the slabs' partial results are added in order — no atomics."""
+    B, R = grad_logits.shape[:2]
+    Bf, C, H, W = mask_features.shape
+    if Bf != B or grad_logits.numel() != B * R * H * W:
+        raise RuntimeError("mask_logits_backward: grad_logits (B,R,H,W) and mask_features (B,C,H,W) disagree")
+    pg, pf = _f32_gpu(grad_logits, "grad_logits"), _f32_gpu(mask_features, "mask_features")
+    dev = grad_logits.device
+    grad_embed = torch.empty((B, R, C), dtype=torch.float32, device=dev)
+    row_sum = torch.empty((B, R), dtype=torch.float32, device=dev)
+    lib = native.lib()
+    nbytes = lib.dvis_mask_logits_backward_ws_bytes(B, R, C, H * W)
+    # per call (46 MB at the training shape): torch's caching allocator hands the same block back step after step
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        rc = lib.dvis_mask_logits_backward(pg, pf, B, R, C, H * W, native.dev_ptr(grad_embed, "grad_embed"),
+                                           native.dev_ptr(row_sum, "row_sum"),
+                                           ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, native.stream_ptr(dev))
+    native.check(rc, "dvis_mask_logits_backward")
+    return grad_embed, row_sum
+
+
+def _mask_logits_grad_features(mask_embed, grad_logits):
+    """einsum("bqc,bqhw->bchw"): the forward contraction with mask_embed transposed and the logit gradient as the map."""
+    Q = mask_embed.shape[1]
+    if Q > 256:
+        raise RuntimeError(f"mask_logits: the gradient with respect to mask_features contracts over the {Q} rows of mask_embed on "
+                           "the forward kernel, which serves at most 256; detach mask_features (a frozen segmenter's map needs no "
+                           "gradient) or call it with fewer rows")
+    return _mask_logits_kernel(mask_embed.transpose(1, 2).contiguous(), grad_logits)
+
+
+class MaskLogitsFunction(Function):
+    """``mask_logits`` under autograd: the forward kernel, csrc/mask_gemm_backward.hip for mask_embed, the forward kernel on
+    transposed operands for mask_features."""
+
+    @staticmethod
+    def forward(ctx, mask_embed, mask_features):
+        ctx.save_for_backward(mask_embed, mask_features)
+        return _mask_logits_kernel(mask_embed, mask_features)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_logits):
+        mask_embed, mask_features = ctx.saved_tensors
+        grad_logits = grad_logits.contiguous()
+        g_embed = g_feat = None
+        if ctx.needs_input_grad[0]:
+            g_embed, _ = mask_logits_backward(grad_logits, mask_features)
+        if ctx.needs_input_grad[1]:
+            g_feat = _mask_logits_grad_features(mask_embed, grad_logits)
+        return g_embed, g_feat
+
+
+def mask_logits(mask_embed, mask_features):
+    """einsum("bqc,bchw->bqhw") of forward_prediction_heads
+    (dvis_Plus/video_mask2former_transformer_decoder.py:363), exact-fp32 MFMA.  (B,Q,C) x (B,C,H,W) -> (B,Q,H,W).
+    Differentiable: an input that requires grad gets its gradient from MaskLogitsFunction (CPU tensors: torch's own)."""
+    B, Q, C = mask_embed.shape
+    Bf, Cf, H, W = mask_features.shape
+    if (Bf, Cf) != (B, C):
+        raise RuntimeError("mask_logits: mask_embed (B,Q,C) and mask_features (B,C,H,W) disagree")
+    if _on_cpu(mask_embed, mask_features):
+        return cpu_ops.mask_logits(mask_embed, mask_features)
+    if torch.is_grad_enabled() and (mask_embed.requires_grad or mask_features.requires_grad):
+        _f32_gpu(mask_embed, "mask_embed"), _f32_gpu(mask_features, "mask_features")
+        return MaskLogitsFunction.apply(mask_embed, mask_features)
+    return _mask_logits_kernel(mask_embed, mask_features)
+
+
+class ProjectedMaskLogitsFunction(Function):
+    """``projected_mask_logits`` on the GPU: see there for the formulas."""
+
+    @staticmethod
+    def forward(ctx, mask_embed, feat, weight, bias):
+        e2 = torch.matmul(mask_embed, weight).contiguous()                    # E' = mask_embed W   (B, R, C_in)
+        logits = _mask_logits_kernel(e2, feat)
+        if bias is not None:
+            logits += torch.matmul(mask_embed, bias)[..., None, None]
+        ctx.save_for_backward(mask_embed, feat, weight, bias)
+        return logits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_logits):
+        mask_embed, feat, weight, bias = ctx.saved_tensors
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("projected_mask_logits: no gradient for the feature map (the segmenter is frozen in the tracker's "
+                               "training stage); detach it")
+        g_e2, row_sum = mask_logits_backward(grad_logits.contiguous(), feat)   # dE' = g feat^T, sum_p g
+        g_embed = g_w = g_b = None
+        if ctx.needs_input_grad[0]:
+            g_embed = torch.matmul(g_e2, weight.t())
+            if bias is not None:
+                g_embed = g_embed + row_sum[..., None] * bias
+        if ctx.needs_input_grad[2]:
+            g_w = torch.matmul(mask_embed.flatten(0, 1).t(), g_e2.flatten(0, 1))
+        if bias is not None and ctx.needs_input_grad[3]:
+            g_b = torch.matmul(mask_embed.flatten(0, 1).t(), row_sum.flatten())
+        return g_embed, None, g_w, g_b
+
+
+def projected_mask_logits(mask_embed, feat, weight, bias=None):
+    """``mask_logits(mask_embed, conv1x1(feat, weight, bias))`` — the tracker's mask head on its own 1 x 1 projection of the
+    segmenter's map (dvis_Plus/tracker.py:199, :379) — WITHOUT the projected map or its gradient ever existing:
+        E' = mask_embed W                      logits = E' feat + (mask_embed b)[..., None]
+        dE' = g feat^T  (csrc/mask_gemm_backward.hip, with row_sum = sum_p g)
+        d mask_embed = dE' W^T + row_sum (x) b      dW = sum mask_embed^T dE'      db = sum mask_embed^T row_sum
+    mask_embed (B, R, C_out), feat (B, C_in, H, W) [no gradient: the segmenter is frozen], weight (C_out, C_in[, 1, 1]), bias
+    (C_out) -> (B, R, H, W).  Everything but the two contractions over the pixels is R x C sized arithmetic.  The summation order
+    differs from project-then-contract by fp32 rounding only."""
+    B, R, Co = mask_embed.shape
+    weight = weight.reshape(weight.shape[0], -1)
+    if weight.shape[0] != Co or feat.shape[:2] != (B, weight.shape[1]):
+        raise RuntimeError("projected_mask_logits: mask_embed (B,R,Co), feat (B,Ci,H,W) and weight (Co,Ci) disagree")
+    if _on_cpu(mask_embed, feat, weight):
+        logits = cpu_ops.mask_logits(torch.matmul(mask_embed, weight), feat)
+        return logits if bias is None else logits + torch.matmul(mask_embed, bias)[..., None, None]
+    _f32_gpu(mask_embed, "mask_embed"), _f32_gpu(feat, "feat")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (mask_embed, feat, weight, bias)):
+        return ProjectedMaskLogitsFunction.apply(mask_embed, feat, weight, bias)
+    with torch.no_grad():
+        return ProjectedMaskLogitsFunction.forward(_NoCtx(), mask_embed, feat, weight, bias)
+
+
+class _NoCtx:
+    def save_for_backward(self, *tensors):
+        pass
 
 
 def attn_mask(mask_embed, mask_features, target_size):

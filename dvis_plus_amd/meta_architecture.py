@@ -19,6 +19,7 @@ Also here: MinVIS (meta_architecture.py:23-407) and the image MaskFormer (mask2f
 """
 import os
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -98,8 +99,8 @@ def segmenter_frames_per_call(n, H, W, requested=0):
 class _VideoBase(nn.Module):
     """Constructor surface of the reference's meta-architectures (dvis_Plus/meta_architecture.py:29-90, 409-500,
     1073-1160): ``Cls(cfg)`` through ``from_config`` like detectron2's ``build_model`` does, or explicit keyword
-    arguments — exactly the reference's names; its training-only ones (criterion, num_frames, max_iter_num, use_cl) are
-    accepted and ignored, anything else is a TypeError;
+    arguments — exactly the reference's names; its training-only ones (criterion, max_iter_num, use_cl) are kept for the
+    training forward of the classes that have one (DVIS_Plus_online) and unused elsewhere, anything else is a TypeError;
     ``metadata`` supplies the thing classes (``thing_dataset_id_to_contiguous_id``), ``n_things`` is the short form
     for datasets whose thing classes are 0..n-1 (VIPSeg)."""
 
@@ -118,6 +119,7 @@ class _VideoBase(nn.Module):
         ids = d2.thing_ids_from_metadata(metadata, video=True)      # meta_architecture.py:919: cls < len(thing table)
         self.thing_ids = frozenset(range(int(n_things))) if ids is None else ids
         self.num_frames, self.window_inference = num_frames, window_inference
+        self.criterion, self.max_iter_num, self.use_cl, self.iter = criterion, max_iter_num, use_cl, 0
         self.size_divisibility = size_divisibility
         self.register_buffer("pixel_mean", torch.tensor(pixel_mean, dtype=torch.float32).view(-1, 1, 1), False)
         self.register_buffer("pixel_std", torch.tensor(pixel_std, dtype=torch.float32).view(-1, 1, 1), False)
@@ -421,12 +423,113 @@ class DVIS_Plus_online(_VideoBase):
         ret["tracker"], _ = cls._tracker_from_config(cfg)
         ret["max_iter_num"] = _get(_get(cfg, "SOLVER", {}), "MAX_ITER", 0)
         ret["use_cl"] = _get(cfg.MODEL.TRACKER, "USE_CL", False)
+        from .criterion import build_criterion
+        # an inference-only config may leave the loss keys out: such a model has no criterion and .train() calls raise
+        if "CLASS_WEIGHT" in cfg.MODEL.MASK_FORMER:
+            ret["criterion"] = build_criterion(cfg, "DVIS_Plus_online")
         return ret
 
-    @torch.no_grad()
-    @Fn.fp32_island
     def forward(self, batched_inputs):
-        assert len(batched_inputs) == 1 and not self.training
+        """.eval(): the reference's output dict of one video.  .train(): the weighted loss dict of the tracker stage."""
+        if self.training:
+            return self._forward_train(batched_inputs)
+        with torch.no_grad():
+            return self._forward_eval(batched_inputs)
+
+    # ---- training (meta_architecture.py:634-686): frozen segmenter under no_grad, trainable tracker
+    @Fn.fp32_island
+    def _forward_train(self, batched_inputs):
+        from .criterion import reference_contrastive_loss
+        assert len(batched_inputs) == 1, "one video per call (the reference's tracker stage indexes batch entry 0 throughout)"
+        if self.criterion is None:
+            raise RuntimeError("DVIS_Plus_online.train() needs a criterion (from_config builds it; criterion.build_criterion)")
+        video = batched_inputs[0]
+        self.keep = bool(video.get("keep", False))
+        self.backbone.eval()
+        self.sem_seg_head.eval()
+        pred = self.sem_seg_head.predictor
+        with torch.no_grad():
+            images, _ = self.preprocess(video["image"])
+
+            def run():
+                with self._x3_scope():
+                    out = self.segment(images)
+                self._guard_verify(self._guard_snapshot())
+                return out
+            try:
+                embds, embds_nn, logits, mask_features = run()
+            except Fn.X3RangeError as e:
+                embds, embds_nn, logits, mask_features = self._x3_rerun(e, run)
+            # the segmenter's own per-frame masks: the matcher's guide during the first half of the schedule
+            C = pred.decoder_norm.weight.shape[0]
+            image_masks = Fn.mask_logits(pred.mask_embed(embds[..., :C].contiguous()).contiguous(), mask_features)      # (T, Q, h, w)
+            object_labels = self._get_instance_labels(logits)
+        to_bctq = lambda z: z.permute(2, 0, 1).unsqueeze(0)
+        outputs, indices = self.tracker(to_bctq(embds), mask_features.unsqueeze(0), return_indices=True, resume=self.keep,
+                                        frame_classes=object_labels, frame_embeds_no_norm=to_bctq(embds_nn))
+        image_outputs = self.reset_image_output_order({"pred_logits": logits, "pred_masks": image_masks}, indices)
+        targets = self.prepare_targets(batched_inputs, images)
+        image_outputs, outputs, targets = self.frame_decoder_loss_reshape(outputs, targets, image_outputs)
+        guide = image_outputs if self.iter < self.max_iter_num // 2 else None
+        losses, match = self.criterion(outputs, targets, matcher_outputs=guide, ret_match_result=True)
+        if self.use_cl:
+            losses.update(reference_contrastive_loss(outputs["pred_references"], match))
+        self.iter += 1
+        weights = self.criterion.weight_dict
+        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+
+    @staticmethod
+    def _get_instance_labels(pred_logits):
+        """(T, Q, K + 1) -> (T, Q) most likely class, -1 for "no object" (meta_architecture.py:708-714)."""
+        labels = pred_logits.argmax(dim=-1)
+        labels[labels == pred_logits.shape[-1] - 1] = -1
+        return labels
+
+    @staticmethod
+    def reset_image_output_order(output, indices):
+        """Segmenter outputs (T, Q, ...) in the order of the tracker's initial queries (meta_architecture.py:742-756)."""
+        idx = torch.as_tensor(np.asarray(indices), dtype=torch.int64, device=output["pred_logits"].device)        # (T, Q)
+        ar = torch.arange(idx.shape[0], device=idx.device)[:, None]
+        return {k: v[ar, idx] for k, v in output.items()}
+
+    def prepare_targets(self, batched_inputs, images):
+        """meta_architecture.py:328-360.  "instances": one object per frame with gt_ids (N), gt_classes (N) and gt_masks (N, h, w)
+        as a tensor or an object with `.tensor`; read by attribute, so detectron2's Instances or any stand-in does."""
+        Hp, Wp = images.shape[-2:]
+        out = []
+        for video in batched_inputs:
+            frames = video["instances"]
+            masks = torch.zeros((len(frames[0].gt_ids), len(frames), Hp, Wp), dtype=torch.bool, device=self.device)
+            ids, classes = [], []
+            for f, inst in enumerate(frames):
+                m = getattr(inst.gt_masks, "tensor", inst.gt_masks).to(self.device)
+                masks[:, f, :m.shape[-2], :m.shape[-1]] = m.bool()
+                ids.append(inst.gt_ids.to(self.device)[:, None])
+                classes.append(inst.gt_classes.to(self.device)[:, None])
+            ids = torch.cat(ids, dim=1)
+            classes = torch.cat(classes, dim=1).max(dim=1)[0]
+            valid = (ids != -1).any(dim=-1)
+            out.append({"labels": classes[valid], "ids": ids[valid], "masks": masks[valid].float()})
+        return out
+
+    @staticmethod
+    def frame_decoder_loss_reshape(outputs, targets, image_outputs=None):
+        """Every frame becomes a batch entry of one frame (meta_architecture.py:716-740)."""
+        def one(d):
+            return {"pred_masks": d["pred_masks"].permute(0, 2, 1, 3, 4).flatten(0, 1).unsqueeze(2),       # b q t h w -> (b t) q 1 h w
+                    "pred_logits": d["pred_logits"].flatten(0, 1)}
+        out = one(outputs)
+        out["pred_references"] = outputs["pred_references"].permute(0, 2, 3, 1).flatten(0, 1)                 # b c t q -> (b t) q c
+        out["aux_outputs"] = [one(a) for a in outputs.get("aux_outputs", ())]
+        if image_outputs is not None:                                                                        # (T, Q, ...) already
+            image_outputs = {"pred_masks": image_outputs["pred_masks"].unsqueeze(2), "pred_logits": image_outputs["pred_logits"]}
+        per_frame = [{"labels": t["labels"], "ids": t["ids"][:, [f]], "masks": t["masks"][:, [f]]}
+                     for t in targets for f in range(t["ids"].shape[1])]
+        return image_outputs, out, per_frame
+
+    @Fn.fp32_island
+    def _forward_eval(self, batched_inputs):
+        assert len(batched_inputs) == 1
         video = batched_inputs[0]
         self.keep = bool(video.get("keep", False))
         images, img_size = self.preprocess(video["image"])
@@ -441,7 +544,7 @@ class DVIS_Plus_online(_VideoBase):
         try:
             self._guard_verify(self._guard_snapshot())     # (the tracker's host-side assignment waits for the segmenter anyway)
         except Fn.X3RangeError as e:
-            return self._x3_rerun(e, lambda: self.forward(batched_inputs))
+            return self._x3_rerun(e, lambda: self._forward_eval(batched_inputs))
         to_bctq = lambda z: z.permute(2, 0, 1).unsqueeze(0)
         track = self.tracker(to_bctq(embds), mask_features.unsqueeze(0), resume=self.keep,
                              frame_embeds_no_norm=to_bctq(embds_nn), need_masks=False)

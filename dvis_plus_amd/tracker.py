@@ -17,12 +17,14 @@ six K/V projections and (offline) a mask einsum whose result is thrown away.  He
 """
 import ctypes
 import os
+import random
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import cpu_ops
 from . import functions as Fn
 from . import native
 from .graphs import FusedKV, GraphRunner
@@ -105,6 +107,74 @@ def cosine_costs(cur, ref_first):
     return 1 - torch.bmm(nrm, ref.transpose(1, 2))
 
 
+class Noiser:
+    """The reference's ``Noiser`` (dvis_Plus/noiser.py): matches the frame's queries to the previous frame's and, in training,
+    replaces the matched initial queries by noised ones with probability `noise_ratio` — 'rs' a random shuffle, 'wa' a random
+    convex mix of every query with a shuffled one, 'cc' the first k channels of the query and the rest of a shuffled one, 'none'
+    nothing.  Every random draw goes through ``_draw`` in the reference's order and shapes, so a test can replay recorded draws;
+    the assignment is the library's own solver (csrc/lsap.cpp) through ``cosine_costs`` / ``match_chains``."""
+
+    def __init__(self, noise_ratio=0.8, mode="wa"):
+        assert mode in ("none", "rs", "wa", "cc")
+        self.mode, self.noise_ratio = mode, noise_ratio
+
+    def _draw(self, kind, *args):
+        """"random" -> float in [0, 1) (random.random); "shuffle", n -> a shuffled list(range(n)) (np.random.shuffle);
+        "rand", shape -> torch.rand(shape); "randint", high, shape -> torch.randint(0, high, shape).  CPU results."""
+        if kind == "random":
+            return random.random()
+        if kind == "shuffle":
+            indices = list(range(args[0]))
+            np.random.shuffle(indices)
+            return indices
+        if kind == "rand":
+            return torch.rand(args[0])
+        if kind == "randint":
+            return torch.randint(0, args[0], args[1])
+        raise ValueError(kind)
+
+    def _rs_noise_forward(self, cur_embeds):
+        indices = self._draw("shuffle", cur_embeds.shape[0])
+        return indices, cur_embeds[indices]
+
+    def _wa_noise_forward(self, cur_embeds):
+        Q = cur_embeds.shape[0]
+        indices = self._draw("shuffle", Q)
+        noise_init = cur_embeds[indices]
+        weight_ratio = self._draw("rand", (Q, 1, 1))
+        noise_init = cur_embeds * weight_ratio.to(cur_embeds) + noise_init * (1.0 - weight_ratio.to(cur_embeds))
+        swapped = (weight_ratio[:, 0, 0] < 0.5).numpy()
+        ret_indices = np.arange(Q, dtype=np.int64)
+        ret_indices[swapped] = np.array(indices)[swapped]
+        return list(ret_indices), noise_init
+
+    def _cc_noise_forward(self, cur_embeds):
+        Q, C = cur_embeds.shape[0], cur_embeds.shape[-1]
+        cut = self._draw("randint", C, (Q,)).unsqueeze(-1).unsqueeze(-1)
+        weight = (torch.arange(C, dtype=torch.int64).view(1, 1, C) < cut).to(torch.float32).to(cur_embeds)
+        indices_, cur_embeds_ = self._rs_noise_forward(cur_embeds)
+        ret_embeds = cur_embeds * weight + cur_embeds_ * (1 - weight)
+        swapped = (cut[:, 0, 0] < C // 2).numpy()
+        ret_indices = np.arange(Q, dtype=np.int64)
+        ret_indices[swapped] = np.array(indices_)[swapped]
+        return list(ret_indices), ret_embeds
+
+    def match_embds(self, ref_embds, cur_embds):
+        """(q, b, c) embeddings -> for every reference row the current query assigned to it (batch entry 0, noiser.py:43-56)."""
+        cost = cosine_costs(cur_embds.detach()[None, :, 0, :], ref_embds.detach()[:, 0, :])
+        cost = torch.where(torch.isnan(cost), torch.zeros_like(cost), cost)
+        return match_chains(cost[None])[0, 0]
+
+    def __call__(self, ref_embeds, cur_embeds, cur_embeds_no_norm=None, activate=False, cur_classes=None):
+        if cur_embeds_no_norm is None:
+            cur_embeds_no_norm = cur_embeds
+        matched_indices = self.match_embds(ref_embeds, cur_embeds)
+        if activate and self._draw("random") < self.noise_ratio and self.mode != "none":
+            noise = {"rs": self._rs_noise_forward, "wa": self._wa_noise_forward, "cc": self._cc_noise_forward}[self.mode]
+            return noise(cur_embeds_no_norm)
+        return matched_indices, cur_embeds_no_norm[matched_indices]
+
+
 class ReferringTracker_noiser(nn.Module):
     def __init__(self, hidden_channel=256, feedforward_channel=2048, num_head=8, decoder_layer_num=6, mask_dim=256,
                  class_num=25, noise_mode="hard", noise_ratio=0.5):
@@ -133,7 +203,10 @@ class ReferringTracker_noiser(nn.Module):
         self.last_outputs = None         # (1 + layers, q, b, c) in the reference; only [-1] is ever read -> (q, b, c)
         self.last_frame_embeds = None
         self.last_reference = None
-        self.noise_mode, self.noise_ratio = noise_mode, noise_ratio   # training-only knobs (kept for the ctor surface)
+        self.noise_mode, self.noise_ratio = noise_mode, noise_ratio
+        # training only (tracker.py:179).  The constructor's default 'hard' is no mode of the reference's Noiser either: it
+        # asserts there at construction, here when the training path is first used.
+        self.noiser = Noiser(noise_ratio=noise_ratio, mode=noise_mode) if noise_mode in ("none", "rs", "wa", "cc") else None
         self._kv_cache = FusedKV("k_v")
         self._q_cache = FusedKV("q")
         self._o_cache = FusedKV("out")
@@ -255,6 +328,88 @@ class ReferringTracker_noiser(nn.Module):
                 last_outputs = outputs[T - 1]
         return outputs, refs, last_outputs
 
+    def _train_layer(self, j, x, reference, key):
+        """Layer j of the training path as torch ops under autograd: referring cross-attention (query `reference`, keys and
+        values the frame's own queries `key`, residual `x`), self-attention, FFN — post-norm, dropout 0 (tracker.py:293-329)."""
+        C = x.shape[-1]
+        ca, sa, ff = (self.transformer_cross_attention_layers[j], self.transformer_self_attention_layers[j],
+                      self.transformer_ffn_layers[j])
+        W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
+        att = cpu_ops.attention(F.linear(reference, W[:C], b[:C]), F.linear(key, W[C:2 * C], b[C:2 * C]),
+                                F.linear(key, W[2 * C:], b[2 * C:]), ca.nhead)
+        x = ca.norm(x + F.linear(att, ca.multihead_attn.out_proj.weight, ca.multihead_attn.out_proj.bias))
+        qkv = F.linear(x, sa.self_attn.in_proj_weight, sa.self_attn.in_proj_bias)
+        att = cpu_ops.attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], sa.nhead)
+        x = sa.norm(x + F.linear(att, sa.self_attn.out_proj.weight, sa.self_attn.out_proj.bias))
+        return ff.norm(x + ff.linear2(torch.relu(ff.linear1(x))))
+
+    def _forward_train(self, frame_embeds, mask_features, resume, return_indices, frame_classes, frame_embeds_no_norm):
+        """The training forward (tracker.py:187-357): layer by layer, the noiser active from frame 1 on, the outputs of all L
+        layers kept and sent through the heads; aux_outputs holds layers 0 .. L - 2.  The layers' 100 x 256 matrices are torch
+        ops under autograd; the mask logits of all layers and frames — the one heavy tensor with a gradient — are ONE
+        Fn.projected_mask_logits call per clip with layers x queries rows per frame."""
+        if self.noiser is None:
+            raise ValueError(f"noise_mode {self.noise_mode!r}: the training path needs one of 'none', 'rs', 'wa', 'cc'")
+        dt = self.decoder_norm.weight.dtype            # fp32; a module moved to double (tests: the fp64 yardstick) stays there
+        frame_embeds, mask_features = frame_embeds.to(dt), mask_features.to(dt)
+        frame_embeds_no_norm = None if frame_embeds_no_norm is None else frame_embeds_no_norm.to(dt)
+        fe = frame_embeds.permute(2, 3, 0, 1)                                  # (t, q, b, c)
+        fe_nn = fe if frame_embeds_no_norm is None else frame_embeds_no_norm.permute(2, 3, 0, 1)
+        T, Q, B, C = fe.shape
+        L = self.num_layers
+        assert B == 1, "the tracker trains one video at a time (the noiser matches on batch entry 0, noiser.py:45)"
+        outputs, references, ret_indices = [], [], []
+        last = self.last_outputs
+        for i in range(T):
+            single, key = fe[i], fe_nn[i]
+            classes = None if frame_classes is None else frame_classes[i]
+            start = i == 0 and not resume
+            if start:
+                self._clear_memory()
+                indices, x = self.noiser(single, single, cur_embeds_no_norm=key, activate=False, cur_classes=classes)
+                reference = None
+            else:
+                reference = self.ref_proj(last)
+                indices, x = self.noiser(self.last_frame_embeds, single, cur_embeds_no_norm=key, activate=self.training,
+                                         cur_classes=classes)
+            self.last_frame_embeds = single[indices]
+            ret_indices.append(indices)
+            layers = []
+            for j in range(L):
+                # frame 0 of a video: every layer's reference is ref_proj of its own input (the frame's queries for layer 0)
+                x = self._train_layer(j, x, reference if not start else self.ref_proj(key if j == 0 else x), key)
+                layers.append(x)
+            self.last_reference = self.ref_proj(key) if start else reference
+            references.append(self.last_reference)
+            last = x
+            outputs.append(torch.stack(layers, dim=0))
+        self.last_outputs = last.detach()                                      # carried state: no graph across calls
+        self.last_reference = self.last_reference.detach()
+        self.last_indices = np.stack([np.asarray(ix, dtype=np.int64) for ix in ret_indices])
+        outputs = torch.stack(outputs, dim=0)                                  # (t, l, q, b, c)
+        references = torch.stack(references, dim=0)                            # (t, q, b, c)
+
+        # ---- heads on every layer (tracker.py:368-380)
+        dec = self.decoder_norm(outputs).permute(1, 3, 0, 2, 4)                # (l, b, t, q, c)
+        refs = references.unsqueeze(1).expand(T, L, Q, B, C).permute(1, 3, 0, 2, 4)
+        outputs_class = self.class_embed(torch.cat([refs, dec], dim=-1))       # (l, b, t, q, K + 1)
+        mask_embed = self.mask_embed(dec)                                      # (l, b, t, q, cm)
+        b_, t_, cm, h, w = mask_features.shape
+        rows = mask_embed[:, 0].permute(1, 0, 2, 3).reshape(T, L * Q, cm)      # a frame's rows: layers x queries
+        proj = self.mask_feature_proj
+        logits = Fn.projected_mask_logits(rows, mask_features[0].detach().contiguous(), proj.weight, proj.bias)   # (t, l q, h, w)
+        outputs_mask = logits.view(T, L, Q, h, w).permute(1, 2, 0, 3, 4).unsqueeze(1)   # (l, b, q, t, h, w)
+        out = {
+            "pred_logits": outputs_class[-1],
+            "pred_masks": outputs_mask[-1],
+            "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(outputs_class[:-1], outputs_mask[:-1])],
+            "pred_embds": outputs[:, -1].permute(2, 3, 0, 1),
+            "pred_references": references.permute(2, 3, 0, 1),
+        }
+        if return_indices:
+            return out, ret_indices
+        return out
+
     @Fn.fp32_island
     def forward(self, frame_embeds, mask_features, resume=False, return_indices=False, frame_classes=None,
                 frame_embeds_no_norm=None, need_masks=True):
@@ -262,7 +417,7 @@ class ReferringTracker_noiser(nn.Module):
         Same outputs as the reference (eval): pred_logits (b,t,q,K+1), pred_masks (b,q,t,h,w) | None,
         pred_embds (b,c,t,q), pred_references (b,c,t,q), aux_outputs []."""
         if self.training:
-            raise NotImplementedError("dvis_plus_amd implements the tracker's inference path")
+            return self._forward_train(frame_embeds, mask_features, resume, return_indices, frame_classes, frame_embeds_no_norm)
         frame_embeds, frame_embeds_no_norm, mask_features = Fn.f32(frame_embeds), Fn.f32(frame_embeds_no_norm), Fn.f32(mask_features)
         fe = frame_embeds.permute(2, 3, 0, 1)                                  # (t, q, b, c)
         fe_nn = fe if frame_embeds_no_norm is None else frame_embeds_no_norm.permute(2, 3, 0, 1)

@@ -16,6 +16,8 @@
  *   dvis_msda_fused_forward  <- softmax + location arithmetic + op of MSDeformAttn.forward,
  *                               ops/modules/ms_deform_attn.py:101-117 (no materialised loc / weights)
  *   dvis_mask_logits         <- einsum("bqc,bchw->bqhw"), dvis_Plus/video_mask2former_transformer_decoder.py:363
+ *   dvis_mask_logits_backward <- autograd's backward of einsum("lbtqc,btchw->lbqthw") with respect to mask_embed (training),
+ *                               dvis_Plus/tracker.py:379 and dvis_Plus/video_mask2former_transformer_decoder.py:363
  *   dvis_attn_mask           <- einsum + F.interpolate + (sigmoid < 0.5) of forward_prediction_heads, ibid. :363-371,
  *                               plus the "fully masked row" reset at :297
  *   dvis_attention_forward   <- nn.MultiheadAttention core (softmax(QK^T/sqrt(d) [+mask]) V) as used by
@@ -200,6 +202,20 @@ int dvis_msda_fused_forward_slots(const float *value, const int64_t *shapes, con
  */
 int dvis_mask_logits(const float *embed, const float *feat, int B, int Q, int C, int64_t HW,
                      float *out, void *stream);
+
+/*
+ * Backward of the mask logits with respect to the embeddings (dvis_Plus/tracker.py:379,
+ * dvis_Plus/video_mask2former_transformer_decoder.py:363), fp32, exact-fp32 MFMA, deterministic (no float atomics):
+ *   grad_embed[b, r, c] = sum_p g[b, r, p] * feat[b, c, p]      row_sum[b, r] = sum_p g[b, r, p]
+ *   g (B, R, HW) = dL/dlogits, feat (B, C, HW), grad_embed (B, R, C), row_sum (B, R).  R = the rows of one frame (in training
+ *   layers x queries, all on the frame's one feature map); C <= 256; R * HW * 4 and C * HW * 4 below 2 GiB.
+ * The pixels are cut into ceil(HW / 4096) slabs — a function of HW alone —, every slab's partial tile goes to `ws` and the
+ * partials are added in slab order: the same inputs give the same bits on every call.  ws: dvis_mask_logits_backward_ws_bytes
+ * bytes (0, and ws may be null, when there is one slab).
+ */
+int64_t dvis_mask_logits_backward_ws_bytes(int B, int R, int C, int64_t HW);
+int dvis_mask_logits_backward(const float *g, const float *feat, int B, int R, int C, int64_t HW, float *grad_embed,
+                              float *row_sum, void *ws, void *stream);
 
 /*
  * Attention mask of the masked-attention decoder, one launch:
