@@ -774,7 +774,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(
 //     -> lane (j, g) holds S[query j][key0 + 4 g + r] = the A layout of the next product: P[query j][keys 4 g ..+3]
 //   O tile (16 queries x 16 dims):    A = P (from registers), B = V[key0 + 4 g ..+3][16 n + j]: four CONSECUTIVE KEYS of one
 //     dim per lane, so V is staged TRANSPOSED ([dim][key], split once per stage by the threads that load it).
-// Scales: Q (already times scale log2 e), K, V by 2^4 (|v| < 4094; elements down to 2^-7 keep 22 bits), P (in [0, 1]) by 2^10;
+// Scales: Q (already times scale log2 e), K, V by 2^4 (|v| < 4095 = 65520 / 2^4; elements down to 2^-7 keep 22 bits), P (in [0, 1]) by 2^10;
 // the score tile is scaled back by 2^-8, the output by 2^-14 inside its 1 / l.  No mask, no key split (callers: nsplit == 1).
 typedef _Float16 ah4 __attribute__((ext_vector_type(4)));
 constexpr int kX3KT = 64;             // keys per stage
@@ -1038,7 +1038,7 @@ __global__ __launch_bounds__(512) void attn_x3_kernel(const _Float16 *__restrict
       }
     }
   }
-  // range guard (x3_common.h): an operand beyond the f16 range (|v| >= 4094) leaves non-finite outputs
+  // range guard (x3_common.h): an operand beyond the f16 range (|v| >= 4095) leaves non-finite outputs
   if (guard_flag != nullptr && chk != chk) atomicCAS(guard_flag, 0, guard_tag);
 }
 

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(kBcWaves * 64) void bneck_chain_kernel(const BcArgs
         for (int q = 0; q < 4; ++q) {
           const f4 b = *(const f4 *)(b2s + 32 * nb + 8 * q + 4 * g);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[nb][4 * q + i] = fmaxf(acc2[nb][4 * q + i] * a.inv2 + b[i], 0.f);
+          for (int i = 0; i < 4; ++i) v[nb][4 * q + i] = x3_relu(acc2[nb][4 * q + i] * a.inv2 + b[i]);
         }
       split_block(v[0], a.xscale, xh, xl);
       split_block(v[1], a.xscale, xh + 2, xl + 2);
@@ -315,7 +315,7 @@ __global__ __launch_bounds__(kBcWaves * 64) void bneck_chain_kernel(const BcArgs
         for (int r = 0; r < 16; ++r) {
           const float t = acc3[nb][r] * a.inv3;
           chk = __builtin_fmaf(t, 0.f, chk);
-          v[r] = fmaxf(t, 0.f);
+          v[r] = x3_relu(t);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[r]), ry, gm.pix, (unsigned)(32 * nb + 8 * (r >> 2) + (r & 3)) * csl, 0);
         }
         asm volatile("" : "+v"(chk));      // (taken here: hipcc otherwise sinks the guard's 128 multiply-adds, and their operands, to the end of the tile)
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(kBcWaves * 64) void bneck_chain_kernel(const BcArgs
           for (int i = 0; i < 4; ++i) {
             const float t = acc1[nb][4 * q + i] * a.inv1 + b[i];
             chk = __builtin_fmaf(t, 0.f, chk);
-            v[4 * q + i] = fmaxf(t, 0.f);
+            v[4 * q + i] = x3_relu(t);
           }
         }
         h8 oh[2], ol[2];

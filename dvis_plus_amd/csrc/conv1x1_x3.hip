@@ -270,7 +270,7 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_x3_kernel(const CxArgs a) {
             for (int i = 0; i < 4; ++i) {
               const float t = acc[nb][4 * q + i] * a.inv + b[i];
               chk = __builtin_fmaf(t, 0.f, chk);
-              v[4 * q + i] = a.relu ? fmaxf(t, 0.f) : t;
+              v[4 * q + i] = a.relu ? x3_relu(t) : t;
             }
           }
           h8 hi[2], lo[2];
@@ -279,6 +279,10 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_x3_kernel(const CxArgs a) {
             const f4 p0 = {v[8 * u], v[8 * u + 1], v[8 * u + 2], v[8 * u + 3]}, p1 = {v[8 * u + 4], v[8 * u + 5], v[8 * u + 6], v[8 * u + 7]};
             split8(p0, p1, a.oscale, hi[u], lo[u]);
           }
+          // ... and the OUTPUT's own window: a value at or beyond 65520 / oscale is stored as (inf, -inf).  |lo| <= 32 otherwise, so
+          // the sum of the 16 low terms is finite exactly when every stored pair is — this launch is named, not its consumer's
+          const h8 ls = lo[0] + lo[1];
+          chk = __builtin_fmaf((float)((ls[0] + ls[1]) + (ls[2] + ls[3]) + (ls[4] + ls[5]) + (ls[6] + ls[7])), 0.f, chk);
           store_fragments4(ri, ibase, hi[0], 4096 * nb, lo[0], 4096 * nb + 1024, hi[1], 4096 * nb + 2048, lo[1], 4096 * nb + 3072);      // (8192 (nb / 2) + 2048 (2 (nb & 1) + u) + 1024 hl)
         }
         if (a.flag != nullptr && chk != chk && p < a.pixels) atomicCAS(a.flag, 0, a.tag);
@@ -304,7 +308,7 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_x3_kernel(const CxArgs a) {
           const unsigned o = obase + (unsigned)(co + i) * ochan;
           float v = acc[nb][4 * q + i] * a.inv + b[i] + rv[4 * q + i];
           chk = __builtin_fmaf(v, 0.f, chk);
-          if (a.relu) v = fmaxf(v, 0.f);
+          if (a.relu) v = x3_relu(v);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, o, 0, 0);
         }
       }

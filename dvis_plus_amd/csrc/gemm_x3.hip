@@ -187,9 +187,9 @@ __device__ __forceinline__ void epilogue(f16v *acc, const EpiArgs &e, const floa
           const float t = acc[nb][4 * q + i] * e.inv + b[i];
           chk = __builtin_fmaf(t, 0.f, chk);
           if constexpr (EX)
-            v[q][i] = e.relu == 1 ? fmaxf(t, 0.f) : e.relu == 2 ? 0.5f * t * (1.f + erff(t * 0.70710678118654752440f)) : t;
+            v[q][i] = e.relu == 1 ? x3_relu(t) : e.relu == 2 ? 0.5f * t * (1.f + erff(t * 0.70710678118654752440f)) : t;
           else
-            v[q][i] = e.relu ? fmaxf(t, 0.f) : t;
+            v[q][i] = e.relu ? x3_relu(t) : t;
         }
       }
     }
@@ -442,8 +442,8 @@ __global__ __launch_bounds__(kThreads) void x3_ffn_kernel(const float *__restric
         const int pair = t >> 1, u = pair >> 2, pp = pair & 3;
         if ((t & 1) == 0) {
           const f2 b = *(const f2 *)(b1s + 128 * hb + 32 * tc + 16 * u + 8 * (pp >> 1) + 4 * g + 2 * (pp & 1));
-          cv[0] = fmaxf(acc1[tc][8 * u + 2 * pp] * f.inv1 + b[0], 0.f) * f.hscale;
-          cv[1] = fmaxf(acc1[tc][8 * u + 2 * pp + 1] * f.inv1 + b[1], 0.f) * f.hscale;
+          cv[0] = x3_relu(acc1[tc][8 * u + 2 * pp] * f.inv1 + b[0]) * f.hscale;
+          cv[1] = x3_relu(acc1[tc][8 * u + 2 * pp + 1] * f.inv1 + b[1]) * f.hscale;
         } else {
           const h2 h = __builtin_convertvector(cv, h2);
           const f2 r = cv - __builtin_convertvector(h, f2);

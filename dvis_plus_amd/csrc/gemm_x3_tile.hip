@@ -166,7 +166,7 @@ __device__ __forceinline__ void tile_store_rows(const TileArgs &a, f16v (&acc)[2
       for (int i = 0; i < 16; ++i) {
         const int64_t m = mrow + 8 * (i >> 2) + (i & 3);
         const float t = acc[mb][nb][i] * a.inv + bv;
-        float v = GELU ? 0.5f * t * (1.f + erff(t * 0.70710678118654752440f)) : a.act == 1 ? fmaxf(t, 0.f) : t;
+        float v = GELU ? 0.5f * t * (1.f + erff(t * 0.70710678118654752440f)) : a.act == 1 ? x3_relu(t) : t;
         if (a.radd) v += rv[i];
         if (full || m < a.M) {
           chk = __builtin_fmaf(t, 0.f, chk);

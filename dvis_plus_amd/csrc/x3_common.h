@@ -45,6 +45,10 @@ __device__ __forceinline__ void dma16(x3_u4 rs, unsigned voff, unsigned so, unsi
 }
 __device__ __forceinline__ unsigned lds_address(const void *p) { return (unsigned)(uintptr_t)(DVIS_LDS const char *)p; }
 
+// ReLU that keeps a NaN (as torch.relu does): fmaxf(NaN, 0) is 0, and a row whose split operand was out of range or not finite
+// would come out of a ReLU epilogue as clean zeros.
+__device__ __forceinline__ float x3_relu(float t) { return t < 0.f ? 0.f : t; }
+
 // v * s -> (hi, lo) for 8 values (round to nearest twice; s is a power of two, so v * s and the residual are exact)
 __device__ __forceinline__ void split8(f4 a, f4 b, float s, h8 &hi, h8 &lo) {
   const float v[8] = {a.x * s, a.y * s, a.z * s, a.w * s, b.x * s, b.y * s, b.z * s, b.w * s};

@@ -1211,8 +1211,8 @@ def x3_range_verify(snap, model=None):
     X3_GUARD.verify(snap, model)
 
 
-X3_XEXP = int(os.environ.get("DVIS_X3_XEXP", "4"))      # activations are scaled by 2^4 before the split (|x| < 4094)
-# the convolutions see ReLU'd feature maps without a normalisation in front: more range (|x| < 16376), an absolute floor of
+X3_XEXP = int(os.environ.get("DVIS_X3_XEXP", "4"))      # activations are scaled by 2^4 before the split (|x| < 4095 = 65520 / 2^4)
+# the convolutions see ReLU'd feature maps without a normalisation in front: more range (|x| < 16380 = 65520 / 2^2), an absolute floor of
 # 2^-27 = 7.5e-9 per element below |x| = 0.03
 X3_CONV_XEXP = int(os.environ.get("DVIS_X3_CONV_XEXP", "2"))
 # conv1x1_bias_act: from this many input channels on a 1x1 layer goes to the split-f16 kernel first — also the memory-bound
@@ -1227,6 +1227,12 @@ def _x3_exp(w):
     return 0 if m == 0.0 or m != m else 14 - math.frexp(m)[1]
 
 
+def _x3_wexp(w):
+    """_x3_exp(w) within the +-60 the pack kernels take: 2^wexp travels as a float, and so does the epilogues' 2^-(xexp + wexp).
+    Only a matrix whose largest element is below 2^-46 (or above 2^74) is affected — one with max|w| below 2^-85 packs as zero."""
+    return max(-60, min(60, _x3_exp(w)))
+
+
 def _x3_cache(key_obj, sources, make, kind="linear"):
     """The split-f16 pack `make()` of `sources`, one per (key_obj, kind) in derived.TABLE; every pack has its own range-guard tag."""
     ent = derived.TABLE.entry(key_obj, kind, sources, make, note=lambda: X3_GUARD.new_tag(key_obj, kind))
@@ -1238,7 +1244,7 @@ def _x3_cache(key_obj, sources, make, kind="linear"):
 
 def _x3_packed(w, nbytes, pack, name):
     """(packed uint8 buffer of `nbytes`, wexp) of the contiguous weight `w` through `pack(wexp, buffer pointer, stream)`."""
-    e = _x3_exp(w)
+    e = _x3_wexp(w)
     buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     with torch.cuda.device(w.device):
         native.check(pack(e, ctypes.c_void_p(buf.data_ptr()), native.stream_ptr(w.device)), name)
@@ -1574,7 +1580,7 @@ def x3_ffn_ln(x, lin1, lin2, norm, pos=None, xexp=None, hexp=None):
 
     def make():
         a, b = w1.detach().contiguous(), w2.detach().contiguous()
-        e1, e2 = _x3_exp(a), _x3_exp(b)
+        e1, e2 = _x3_wexp(a), _x3_wexp(b)
         buf = torch.empty(native.lib().dvis_x3_ffn_packed_bytes(K, H, N), dtype=torch.uint8, device=a.device)
         with torch.cuda.device(a.device):
             native.check(native.lib().dvis_x3_ffn_pack(ctypes.c_void_p(a.data_ptr()), K, ctypes.c_void_p(b.data_ptr()), H, K, H,
@@ -1967,8 +1973,8 @@ def bneck_stage_x3(x, blocks, xexp=None):
             w3 = b["w3"].detach().reshape(256, 64).contiguous()
             wsd = None if ws is None else ws.detach().reshape(256, 64).contiguous()
             w1d = None if w1n is None else w1n.detach().reshape(64, 256).contiguous()
-            e2, e1 = _x3_exp(w2), (0 if w1d is None else _x3_exp(w1d))
-            e3 = _x3_exp(w3 if wsd is None else torch.cat([w3, wsd], 1))
+            e2, e1 = _x3_wexp(w2), (0 if w1d is None else _x3_wexp(w1d))
+            e3 = _x3_wexp(w3 if wsd is None else torch.cat([w3, wsd], 1))
             buf = torch.empty(lib.dvis_bneck_x3_packed_bytes(0 if w1d is None else 1, 0 if wsd is None else 1), dtype=torch.uint8, device=dev)
             with torch.cuda.device(dev):
                 native.check(lib.dvis_bneck_x3_pack(native.dev_ptr(w2, "w2"), native.dev_ptr(w3, "w3"),

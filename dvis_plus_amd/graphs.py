@@ -8,6 +8,7 @@ Inputs are copied into static buffers, outputs are returned as views of static b
 of the same graph — callers consume them within the clip or clone).
 """
 import collections
+import gc
 
 import torch
 
@@ -42,9 +43,20 @@ class GraphRunner:
                     self.fn(*static_in)
             cur.wait_stream(side)
             graph = torch.cuda.CUDAGraph()
-            # thread_local: other threads (e.g. the RCCL watchdog) may keep querying events while we capture
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                static_out = self.fn(*static_in)
+            # No cyclic garbage collection inside the capture: a dead cycle that holds an older hipGraph (a dropped model's
+            # runners) frees that graph's memory pool in its destructor, which is not allowed while a stream captures and ends
+            # the process.  torch.cuda.graph no longer collects before it begins, so it is done here, and the collector stays
+            # off until the capture has ended.
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                # thread_local: other threads (e.g. the RCCL watchdog) may keep querying events while we capture
+                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    static_out = self.fn(*static_in)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             entry = (graph, static_in, static_out)
             self._cache[key] = entry
             while len(self._cache) > self.max_entries:

@@ -270,7 +270,7 @@ int dvis_attention_forward_k(const float *q, const int64_t *q_strides, const flo
  * dvis_Plus/../vit_adapter: 3681 tokens x 16 heads at 720p) on split-f16 matrix-core products — Q, K, V as two f16 terms each
  * (x3_common.h: three products per fp32 product, fp32 accumulation), softmax in fp32, the probabilities split the same way.
  * Two launches: the operands' two-term images are written once into `ws` (dvis_attention_ws_bytes_k(.., 2) bytes: what Q, K, V
- * take in fp32), then one workgroup per (batch-head, 128 queries) streams K / V from there.  Operands must stay below 4094 in
+ * take in fp32), then one workgroup per (batch-head, 128 queries) streams K / V from there.  Operands must stay below 4095 (65520 / 2^4) in
  * magnitude (the range guard of dvis_x3_set_range_flag reports a violation). */
 int64_t dvis_attention_ws_bytes_k(int BH, int Lq, int Lk, int d, int kernel);
 
@@ -560,7 +560,7 @@ int dvis_gemm_ln_pick_config(int M, int N, int K);
  * three matrix-core products lo*hi + hi*lo + hi*hi accumulated in fp32; the result is scaled back by 2^-(xexp + wexp).
  * Measured against fp64 the error is that of an fp32 GEMM (its accumulation rounding dominates; tests/test_gemm_x3_gpu.py).
  * xexp / wexp / hexp: the power-of-two exponents the activations / weights / hidden activations are scaled by before the
- * split; |v 2^e| must stay below 65504 (f16 range; values beyond saturate to +-inf in the hi term).
+ * split; |v 2^e| must stay below 65520 (f16 range: from 65520 on the hi term rounds to +-inf).
  *
  * dvis_x3_pack: W (N x K, row stride ldw) -> `packed` (dvis_x3_packed_bytes(N, K) bytes), the kernels' LDS image (1 KB
  * fragments [pass][k-step][row block][hi, lo][lane][8 halves]; N = 288: ten row blocks per k-step, the tenth zero, so that an item's
@@ -573,8 +573,9 @@ int64_t dvis_x3_packed_bytes(int N, int K);
 int dvis_x3_set_reserve(int cus);
 /* Range guard of the split-f16 kernels.  The reference computes this path in fp32 (an explicit fp32 island,
  * mask2former/modeling/pixel_decoder/msdeformattn.py:314,320): no activation magnitude breaks it.  Here an activation with
- * |v 2^xexp| >= 65520 becomes (inf, -inf) in the split and its output row non-finite — which a following ReLU would turn into
- * plain zeros.  Every dvis_x3_* / dvis_conv*_x3 launch therefore tests its PRE-activation outputs and, on a non-finite value,
+ * |v 2^xexp| >= 65520 becomes (inf, -inf) in the split and its output row non-finite; the epilogues' ReLU keeps a NaN (as torch.relu does), but a
+ * pre-activation of -inf would still leave it as 0.  Every dvis_x3_* / dvis_conv*_x3 launch therefore tests its PRE-activation outputs
+ * (an operand-image epilogue also the values it stores against the image's own exponent) and, on a non-finite value,
  * stores the launch's tag (dvis_x3_set_tag, per host thread, > 0; returns the previous tag) into the int32 device word
  * registered for the current device (dvis_x3_set_range_flag; NULL = guard off, the default).  The word is sticky: the host
  * zeroes it, reads it once per clip and maps the tag back to the layer (dvis_plus_amd/functions.py: X3RangeError). */
