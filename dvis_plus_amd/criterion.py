@@ -8,6 +8,8 @@ torch's cross_entropy ((B, Q, C + 1): not a hot path).  Half / bf16 mask logits 
 samples in half and upcasts after).  Every random draw goes through ``_rand`` in the reference's order and shapes:
 (R, int(num_points * oversample_ratio), 2) then (R, num_points - int(importance_sample_ratio * num_points), 2) per loss_masks.
 """
+import random
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -177,6 +179,79 @@ def reference_contrastive_loss(references, match_result):
     cos = torch.einsum("nqc,nc->nq", F.normalize(other, dim=2), F.normalize(anchor, dim=1))
     aux = (cos - F.one_hot(rows, Q).to(cos.dtype)).square().mean()
     return {"loss_reid": reid, "loss_aux_reid": aux}
+
+
+class Outputs_Memory_PerClasses:
+    """The refiner stage's class-reference memory (dvis_Plus/utils.py:4-49, the part DVIS_Plus_offline uses): per class a list of
+    embedding rows of earlier clips, detached, the negatives of ``refiner_contrastive_loss``'s class items.  A class that grows
+    past ``max_len`` rows is shuffled and cut to its last ``max_len``; the shuffle is the memory's one random draw and goes through
+    ``_draw`` so that recorded draws can be replayed."""
+
+    def __init__(self, max_len=100):
+        self.class_references = {}
+        self.max_len = max_len
+
+    def _draw(self, kind, n):
+        """"shuffle", n -> a shuffled list(range(n)) (random.shuffle)."""
+        if kind != "shuffle":
+            raise ValueError(kind)
+        indices = list(range(n))
+        random.shuffle(indices)
+        return indices
+
+    def push_refiner(self, references, targets, match_result):
+        """references (T, Q, C); targets: the video's target dict ("labels"); match_result (query rows, target rows): every matched
+        query's T rows join its target's class."""
+        references = references.clone().detach()
+        classes = targets["labels"]
+        for r, g in zip(match_result[0].tolist(), match_result[1].tolist()):
+            self.class_references.setdefault(int(classes[g]), []).extend(torch.unbind(references[:, r], dim=0))
+        for cls, rows in self.class_references.items():
+            if len(rows) > self.max_len:
+                order = self._draw("shuffle", len(rows))
+                self.class_references[cls] = [rows[i] for i in order][-self.max_len:]
+
+    def get_items(self, cls):
+        rows = self.class_references.get(cls)
+        return torch.stack(rows, dim=0) if rows else []
+
+
+def refiner_contrastive_loss(pred_embds, match, labels, memory):
+    """DVIS_Plus_offline.get_cl_loss_with_memory + loss_reid (dvis_Plus/meta_architecture.py:1502-1579, dvis_Plus/utils.py:51-94) in
+    a batched form.  pred_embds (T, Q, C): the refiner's "pred_embds", one row of queries per frame; match = (query rows, target
+    rows) of the video; labels (G) the targets' classes; memory: an Outputs_Memory_PerClasses.
+    For every frame t and matched (query r, target g) one instance item: anchor = row r of frame t, positives = row r of all T
+    frames (t included), negatives = the other Q - 1 rows of frame t; and, where the memory holds rows of g's class, one class
+    item with the same anchor and positives and the memory's rows as negatives.
+    loss_reid = mean over the items of logsumexp over all (negative - positive) . anchor pairs and one 0; loss_aux_reid = mean
+    over the items of the mean squared difference between cosine and label (1 positive, 0 negative).  The clip's matched rows are
+    then pushed into the memory.  No matched pair: both are 0 with a graph to `pred_embds`."""
+    T, Q, C = pred_embds.shape
+    by_target = {}
+    for r, g in zip(match[0].tolist(), match[1].tolist()):
+        by_target[g] = r
+    reid, aux = [], []
+    unit = F.normalize(pred_embds, dim=2)
+    for g, r in by_target.items():
+        anchor, u_anchor = pred_embds[:, r], unit[:, r]                            # (T, C): one anchor per frame
+        pos = anchor @ anchor.t()                                                  # (T anchors, T positives)
+        cos_pos = u_anchor @ u_anchor.t()
+        others = [q for q in range(Q) if q != r]
+        negatives = [(torch.einsum("tqc,tc->tq", pred_embds[:, others], anchor),
+                      torch.einsum("tqc,tc->tq", unit[:, others], u_anchor))]
+        rows = memory.get_items(int(labels[g]))
+        if len(rows):
+            rows = rows.to(pred_embds)
+            negatives.append((anchor @ rows.t(), u_anchor @ F.normalize(rows, dim=1).t()))
+        for neg, cos_neg in negatives:                                            # (T, N) each
+            pairs = (neg[:, None, :] - pos[:, :, None]).flatten(1)                 # (T, T * N)
+            reid.append(torch.logsumexp(F.pad(pairs, (0, 1)), dim=1))
+            aux.append(((cos_pos - 1).square().sum(1) + cos_neg.square().sum(1)) / (T + neg.shape[1]))
+    memory.push_refiner(pred_embds, {"labels": labels}, match)
+    if not reid:
+        zero = pred_embds.sum() * 0
+        return {"loss_reid": zero, "loss_aux_reid": zero}
+    return {"loss_reid": torch.cat(reid).mean(), "loss_aux_reid": torch.cat(aux).mean()}
 
 
 def build_criterion(cfg, meta_arch=None):

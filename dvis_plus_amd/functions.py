@@ -493,12 +493,27 @@ def attention(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=Fa
     Returns (Lq, B, C) ready for the out-projection.
     short=True pins the short-key latency kernel (Lk <= 128) whatever the batch size: same bits per (batch, head) for a clip
     alone or stacked with others (the tracker's recurrence).
+    Differentiable without a mask: an input that requires grad routes the call through AttentionFunction (same forward kernel,
+    same bits; CPU tensors: torch's own autograd).
     """
+    if _on_cpu(q, k, v):
+        return cpu_ops.attention(q, k, v, nheads, mask, allowed_count, out)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        if mask is not None:
+            raise RuntimeError("attention: no gradient through a masked attention (csrc/attention_backward.hip serves mask=None); "
+                               "detach q / k / v or call it without a mask")
+        if out is not None:
+            raise RuntimeError("attention: out= cannot be combined with an input that requires grad (the result must be a new "
+                               "tensor of the autograd graph)")
+        _attention_backward_check(q, k, v, None, nheads)
+        return AttentionFunction.apply(q, k, v, nheads, short)
+    return _attention_kernel(q, k, v, nheads, mask, allowed_count, out, short)
+
+
+def _attention_kernel(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=False):
     Lq, B, C = q.shape
     Lk = k.shape[0]
     d = C // nheads
-    if _on_cpu(q, k, v):
-        return cpu_ops.attention(q, k, v, nheads, mask, allowed_count, out)
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 3 or t.stride(2) != 1:
             raise RuntimeError(f"attention: {name} must be a float32 GPU (L, B, C) tensor with a contiguous last dim")
@@ -533,6 +548,79 @@ def attention(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=Fa
             ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, native.stream_ptr(q.device), kern)
     native.check(rc, "dvis_attention_forward")
     return out
+
+
+ATTENTION_BACKWARD_MAX_KEYS = 256
+
+
+def _attention_backward_check(q, k, v, grad_out, nheads):
+    """The contract of csrc/attention_backward.hip, checked on the host before anything is launched."""
+    tensors = [("q", q), ("k", k), ("v", v)] + ([("grad_out", grad_out)] if grad_out is not None else [])
+    for name, t in tensors:
+        if not t.is_cuda or t.dim() != 3:
+            raise RuntimeError(f"attention_backward: {name} must be a GPU (L, B, C) tensor")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"attention_backward: {name} must be float32 (got {t.dtype})")
+        if t.stride(2) != 1:
+            raise RuntimeError(f"attention_backward: {name} must have inner stride 1 (got {t.stride(2)})")
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or (grad_out is not None and grad_out.shape != q.shape):
+        raise RuntimeError("attention_backward: inconsistent q / k / v / grad_out shapes")
+    if C % nheads or C // nheads not in (32, 64):
+        raise RuntimeError(f"attention_backward: head dim must be 32 or 64 (got C={C} over {nheads} heads)")
+    if Lk > ATTENTION_BACKWARD_MAX_KEYS:
+        raise RuntimeError(f"attention_backward: serves at most {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
+    if Lq < 1 or Lk < 1:
+        raise RuntimeError(f"attention_backward: needs Lq >= 1 and Lk >= 1 (got Lq={Lq}, Lk={Lk})")
+
+
+def attention_backward(q, k, v, grad_out, nheads):
+    """Gradients of ``attention(q, k, v, nheads)`` (no mask) for the upstream gradient ``grad_out`` (csrc/attention_backward.hip):
+    q / grad_out (Lq, B, C), k / v (Lk, B, C) float32 GPU tensors with unit inner stride and arbitrary row / batch strides, head dim
+    32 or 64, Lk <= 256 -> (dq (Lq, B, C), dk (Lk, B, C), dv (Lk, B, C)), contiguous.  The probabilities are recomputed from q and
+    k.  Exact fp32, no atomics: the same bits on every call, and a batch entry's bits do not depend on B.  Anything outside the
+    contract raises before a launch; there is no torch formulation behind it for GPU tensors."""
+    _attention_backward_check(q, k, v, grad_out, nheads)
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    d = C // nheads
+    dev = q.device
+    dq = torch.empty((Lq, B, C), dtype=torch.float32, device=dev)
+    dk = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    dv = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    if B == 0:
+        return dq, dk, dv
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_attention_backward(
+            ptr(q), _strides3(q, B, C, d), ptr(k), _strides3(k, B, C, d), ptr(v), _strides3(v, B, C, d), ptr(grad_out),
+            _strides3(grad_out, B, C, d), ptr(dq), ptr(dk), ptr(dv), B, nheads, Lq, Lk, d, 1.0 / (d ** 0.5), native.stream_ptr(dev))
+    native.check(rc, "dvis_attention_backward")
+    return dq, dk, dv
+
+
+class AttentionFunction(Function):
+    """``attention`` (no mask) under autograd: the forward kernel as it is, csrc/attention_backward.hip for all three inputs."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nheads, short):
+        ctx.save_for_backward(q, k, v)
+        ctx.nheads = nheads
+        return _attention_kernel(q, k, v, nheads, short=short)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v = ctx.saved_tensors
+        # the kernel's view contract: unit inner stride, 16-byte aligned base, row / batch strides in multiples of 4 floats.  What
+        # autograd hands over need not meet it (the narrowed gradient of a concatenation, an odd stride on a dim of size 1): copy
+        B = grad_out.shape[1]
+        if grad_out.stride(2) != 1 or grad_out.data_ptr() % 16 or grad_out.stride(0) % 4 or (B > 1 and grad_out.stride(1) % 4):
+            grad_out = grad_out.contiguous()
+        dq, dk, dv = attention_backward(q, k, v, grad_out, ctx.nheads)
+        need = ctx.needs_input_grad
+        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None
 
 
 def vps_argmax(mask_logits_kthw, scores, first_resize_size, img_size, out_hw):

@@ -581,7 +581,95 @@ class DVIS_Plus_offline(_VideoBase):
                                          windows=_get(mf.TEST, "WINDOW_SIZE", 3))
         ret["max_iter_num"] = _get(_get(cfg, "SOLVER", {}), "MAX_ITER", 0)
         ret["use_cl"] = _get(cfg.MODEL.REFINER, "USE_CL", False)
+        from .criterion import build_criterion
+        # an inference-only config may leave the loss keys out: such a model has no criterion and .train() calls raise
+        if "CLASS_WEIGHT" in cfg.MODEL.MASK_FORMER:
+            crit = build_criterion(cfg, "DVIS_Plus_offline")
+            # The criterion built HERE keeps its one buffer (class weights, a function of NUM_CLASSES and NO_OBJECT_WEIGHT alone)
+            # out of the model's state_dict: `DVIS_Plus_offline(cfg)` from the reference's yaml is pinned key for key to
+            # tests/golden/ref_state_shapes_dvis_plus_r50.json (tests/test_d2_protocol.py), which has no criterion entry, and the
+            # yaml carries the loss keys.  A criterion the caller passes in is left as it is.
+            crit.register_buffer("empty_weight", crit.empty_weight, persistent=False)
+            ret["criterion"] = crit
         return ret
+
+    def __init__(self, *args, **kwargs):
+        """meta_architecture.py:1153-1159: the refiner stage trains the refiner alone — the tracker's parameters are frozen here,
+        the segmenter runs under no_grad — and keeps a class-reference memory for its contrastive loss."""
+        super().__init__(*args, **kwargs)
+        from .criterion import Outputs_Memory_PerClasses
+        if self.tracker is not None:
+            for p in self.tracker.parameters():
+                p.requires_grad_(False)
+        self.classes_references_memory = Outputs_Memory_PerClasses(max_len=20)
+
+    prepare_targets = DVIS_Plus_online.prepare_targets
+    _get_instance_labels = staticmethod(DVIS_Plus_online._get_instance_labels)
+
+    # ---- training (meta_architecture.py:1264-1375): frozen segmenter and tracker under no_grad, trainable refiner
+    @Fn.fp32_island
+    def _forward_train(self, batched_inputs):
+        from .criterion import refiner_contrastive_loss
+        assert len(batched_inputs) == 1, "one video per call (the reference's refiner stage indexes batch entry 0 throughout)"
+        if self.criterion is None:
+            raise RuntimeError("DVIS_Plus_offline.train() needs a criterion (from_config builds it; criterion.build_criterion)")
+        if self.clip_shard.world > 1:
+            raise RuntimeError("DVIS_Plus_offline.train(): multi-GPU training (sharded or streamed) is not built; train on one GPU")
+        video = batched_inputs[0]
+        self.keep = bool(video.get("keep", False))
+        self.backbone.eval()
+        self.sem_seg_head.eval()
+        self.tracker.eval()
+        to_bctq = lambda z: z.permute(2, 0, 1).unsqueeze(0)
+        with torch.no_grad():
+            images, _ = self.preprocess(video["image"])
+
+            def run():
+                with self._x3_scope():
+                    out = self.segment(images)
+                self._guard_verify(self._guard_snapshot())
+                return out
+            try:
+                embds, embds_nn, logits, mask_features = run()
+            except Fn.X3RangeError as e:
+                embds, embds_nn, logits, mask_features = self._x3_rerun(e, run)
+            mask_features = mask_features.unsqueeze(0)
+            track = self.tracker(to_bctq(embds), mask_features, resume=self.keep, frame_classes=self._get_instance_labels(logits),
+                                 frame_embeds_no_norm=to_bctq(embds_nn))
+            # the tracker's own prediction: the matcher's guide during the first half of the schedule
+            image_outputs = {"pred_logits": track["pred_logits"], "pred_masks": track["pred_masks"]}
+            instance_embeds, frame_embeds = track["pred_embds"].clone(), to_bctq(embds_nn).clone()
+        outputs = self.refiner(instance_embeds, frame_embeds, mask_features)
+        targets = self.prepare_targets(batched_inputs, images)
+        guide = image_outputs if self.iter < self.max_iter_num // 2 else None
+        guide, outputs, targets = self.frame_decoder_loss_reshape(outputs, targets, guide)
+        self.iter += 1
+        losses, match = self.criterion(outputs, targets, matcher_outputs=guide, ret_match_result=True)
+        if self.use_cl:
+            losses.update(refiner_contrastive_loss(outputs["pred_embds"][0].permute(1, 2, 0), match[0], targets[0]["labels"],
+                                                   self.classes_references_memory))
+        weights = self.criterion.weight_dict
+        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+
+    @staticmethod
+    def frame_decoder_loss_reshape(outputs, targets, image_outputs=None):
+        """The T frames of a clip become one (T h, w) image (meta_architecture.py:1424-1444); the guide's class logits are
+        averaged over the frames."""
+        def one(d):
+            b, q, t, h, w = d["pred_masks"].shape
+            return {"pred_masks": d["pred_masks"].reshape(b, q, 1, t * h, w), "pred_logits": d["pred_logits"][:, 0]}
+        out = one(outputs)
+        out["pred_embds"] = outputs["pred_embds"]
+        out["aux_outputs"] = [one(a) for a in outputs.get("aux_outputs", ())]
+        if image_outputs is not None:
+            b, q, t, h, w = image_outputs["pred_masks"].shape
+            image_outputs = {"pred_masks": image_outputs["pred_masks"].reshape(b, q, 1, t * h, w),
+                             "pred_logits": image_outputs["pred_logits"].mean(dim=1)}
+        flat = []
+        for t_ in targets:
+            g, t, h, w = t_["masks"].shape
+            flat.append({**t_, "masks": t_["masks"].reshape(g, 1, t * h, w)})
+        return image_outputs, out, flat
 
     # ---- the clip as two phases: everything up to the per-frame queries is asynchronous and rank-local (phase A);
     # everything after needs the other ranks' queries, host-side assignment and the VPS statistics (phase B).
@@ -963,9 +1051,15 @@ class DVIS_Plus_offline(_VideoBase):
             th.join()
             main.wait_stream(self._tracker_stream)
 
+    def forward(self, batched_inputs):
+        """.eval(): the reference's output dict of one video.  .train(): the weighted loss dict of the refiner stage."""
+        if self.training:
+            return self._forward_train(batched_inputs)
+        return self._forward_eval(batched_inputs)
+
     @torch.no_grad()
     @Fn.fp32_island
-    def forward(self, batched_inputs):
+    def _forward_eval(self, batched_inputs):
         assert len(batched_inputs) == 1 and not self.training
         video = batched_inputs[0]
         if self.pipeline_rounds <= 1:

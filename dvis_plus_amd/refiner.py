@@ -1,7 +1,7 @@
 """Temporal refiner — host side of SURVEY.md §8 row a11.
 
 Mirrors ``TemporalRefiner`` (dvis_Plus/refiner.py:6-227): constructor arguments, ``state_dict`` keys, call signature
-and returned dict (eval branch: last layer only, window-free).
+and returned dict (eval branch: last layer only, window-free; training branch: all layers, aux_outputs).
 
 MI355X re-organisation:
   * one activation layout (T, Q, C) for all four sub-layers: the attention kernel takes row / batch strides, so "over
@@ -121,6 +121,77 @@ class TemporalRefiner(nn.Module):
                 x = self.transformer_ffn_layers[i](x)
         return x.view(T, B, Q, C).transpose(1, 2)                                  # (t, q, b, c)
 
+    # ---- training (refiner.py:91-158, 196-227): torch ops under autograd around the attention kernel and its backward ---------
+
+    def _train_attention(self, q, k, v, over_time):
+        """q / k / v (T, Q, C) views of ONE clip with unit inner stride -> (T, Q, C).  Fn.attention is differentiable: GPU tensors
+        take the forward kernel and csrc/attention_backward.hip, CPU tensors the torch formulation.  Over the queries of a frame the
+        batch entries are the frames: the transposed view, no copy."""
+        if over_time:
+            return Fn.attention(q, k, v, self.num_heads)
+        return Fn.attention(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1), self.num_heads).transpose(0, 1)
+
+    def _train_self_attention(self, layer, x, over_time):
+        C = x.shape[-1]
+        qkv = F.linear(x, layer.self_attn.in_proj_weight, layer.self_attn.in_proj_bias)
+        att = self._train_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], over_time)
+        op = layer.self_attn.out_proj
+        return layer.norm(x + F.linear(att, op.weight, op.bias))
+
+    def _train_short_aggregate(self, i, x):
+        """``_short_aggregate`` with F.linear on the weights themselves (no cached re-layout: the gradient must reach them)."""
+        T = x.shape[0]
+        for conv, relu in ((self.conv_short_aggregate_layers[i][0], True), (self.conv_short_aggregate_layers[i][2], False)):
+            k = conv.kernel_size[0]
+            idx = (torch.arange(T, device=x.device)[:, None] + torch.arange(k, device=x.device)[None] - k // 2).clamp_(0, T - 1)
+            cols = x[idx].permute(0, 2, 1, 3).flatten(2)                           # (T, Q, k * C)
+            x = F.linear(cols, conv.weight.permute(0, 2, 1).flatten(1), conv.bias)
+            x = torch.relu(x) if relu else x
+        return x
+
+    def _forward_train(self, instance_embeds, frame_embeds, mask_features):
+        """The training forward: the outputs of all L layers are kept and sent through decoder_norm and the heads; aux_outputs
+        holds layers 0 .. L - 2.  The layers work on the one (T, Q, C) layout of ``refine``; the mask logits of all layers and
+        frames are ONE Fn.mask_logits call with layers x queries rows per frame (backward: csrc/mask_gemm_backward.hip), on
+        mask_features as a constant.  No graph capture here."""
+        dt = self.decoder_norm.weight.dtype            # fp32; a module moved to double (tests: the fp64 yardstick) stays there
+        instance_embeds, frame_embeds, mask_features = instance_embeds.to(dt), frame_embeds.to(dt), mask_features.to(dt)
+        B, C, T, Q = instance_embeds.shape
+        assert B == 1, "the refiner trains one video at a time"
+        L = self.num_layers
+        x = instance_embeds.permute(2, 0, 3, 1).reshape(T, Q, C)
+        fe = frame_embeds.permute(2, 0, 3, 1).reshape(T, Q, C)
+        layers = []
+        for i in range(L):
+            x = self._train_self_attention(self.transformer_time_self_attention_layers[i], x, over_time=True)
+            x = self.conv_norms[i](self._train_short_aggregate(i, x) + x)
+            x = self._train_self_attention(self.transformer_obj_self_attention_layers[i], x, over_time=False)
+            ca = self.transformer_cross_attention_layers[i]
+            W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
+            att = self._train_attention(F.linear(x, W[:C], b[:C]), F.linear(fe, W[C:2 * C], b[C:2 * C]),
+                                        F.linear(fe, W[2 * C:], b[2 * C:]), over_time=False)
+            x = ca.norm(x + F.linear(att, ca.multihead_attn.out_proj.weight, ca.multihead_attn.out_proj.bias))
+            ff = self.transformer_ffn_layers[i]
+            x = ff.norm(x + ff.linear2(torch.relu(ff.linear1(x))))
+            layers.append(x)
+        dec = self.decoder_norm(torch.stack(layers, dim=0)).unsqueeze(1)          # (l, b, t, q, c)
+        # ---- heads on every layer (refiner.py:196-223)
+        ap, ce = self.activation_proj, self.class_embed
+        activation = F.linear(dec, ap.weight, ap.bias).softmax(dim=2)
+        pooled = (dec * activation).sum(dim=2, keepdim=True).repeat(1, 1, T, 1, 1)
+        outputs_class = F.linear(pooled, ce.weight, ce.bias)                       # (l, b, t, q, K + 1)
+        emb = dec
+        for j, lin in enumerate(self.mask_embed.layers):
+            emb = F.linear(emb, lin.weight, lin.bias)
+            emb = torch.relu(emb) if j < self.mask_embed.num_layers - 1 else emb
+        b_, t_, cm, h, w = mask_features.shape
+        rows = emb[:, 0].permute(1, 0, 2, 3).reshape(T, L * Q, cm)                # a frame's rows: layers x queries
+        logits = Fn.mask_logits(rows, mask_features[0].detach().contiguous())     # (t, l q, h, w)
+        outputs_mask = logits.view(T, L, Q, h, w).permute(1, 2, 0, 3, 4).unsqueeze(1)   # (l, b, q, t, h, w)
+        return {"pred_logits": outputs_class[-1], "pred_masks": outputs_mask[-1],
+                "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(outputs_class[:-1], outputs_mask[:-1])],
+                "pred_embds": dec[-1].permute(0, 3, 1, 2)}
+
     def pred_class(self, decoder_output):
         """(l, b, t, q, c): softmax-over-time pooled class logits, repeated T times (refiner.py:196-210)."""
         T = decoder_output.size(2)
@@ -135,7 +206,7 @@ class TemporalRefiner(nn.Module):
         Returns pred_logits (b,t,q,K+1), pred_masks (b,q',t,h,w) [q' = len(query_index) if given] or None,
         pred_embds (b,c,t,q), mask_embed (b,t,q,Cm)."""
         if self.training:
-            raise NotImplementedError("dvis_plus_amd implements the refiner's inference path")
+            return self._forward_train(instance_embeds, frame_embeds, mask_features)
         instance_embeds, frame_embeds, mask_features = Fn.f32(instance_embeds), Fn.f32(frame_embeds), Fn.f32(mask_features)
         self._kv_weights()
         for seq in self.conv_short_aggregate_layers:                               # cached GEMM weights, outside capture

@@ -23,6 +23,8 @@
  *   dvis_attention_forward   <- nn.MultiheadAttention core (softmax(QK^T/sqrt(d) [+mask]) V) as used by
  *                               CrossAttentionLayer / SelfAttentionLayer (mask2former_video/.../video_mask2former_transformer_decoder.py:18-136),
  *                               ReferringCrossAttentionLayer (dvis_Plus/tracker.py:8-92), TemporalRefiner (dvis_Plus/refiner.py:104-139)
+ *   dvis_attention_backward  <- autograd's backward of that core without a mask (training of the temporal refiner,
+ *                               dvis_Plus/refiner.py:104-139)
  *   dvis_add_layernorm       <- `norm(tgt + tgt2)` of every post-norm residual block (msdeformattn.py:125-131,
  *                               video_mask2former_transformer_decoder.py:47-50,108-111,166-170, tracker.py:51-53)
  *   dvis_nchw_to_tokens      <- src.flatten(2).transpose(1, 2) + torch.cat over levels, msdeformattn.py:64-79
@@ -273,6 +275,22 @@ int dvis_attention_forward_k(const float *q, const int64_t *q_strides, const flo
  * take in fp32), then one workgroup per (batch-head, 128 queries) streams K / V from there.  Operands must stay below 4095 (65520 / 2^4) in
  * magnitude (the range guard of dvis_x3_set_range_flag reports a violation). */
 int64_t dvis_attention_ws_bytes_k(int BH, int Lq, int Lk, int d, int kernel);
+
+/*
+ * Backward of softmax(Q K^T * scale) V without a mask, fp32, exact fp32 FMA arithmetic, deterministic (no float atomics):
+ *   P = softmax(Q K^T * scale)   dV = P^T dO   dP = dO V^T   D = rowsum(P o dP)   dS = P o (dP - D)
+ *   dQ = scale * dS K            dK = scale * dS^T Q
+ * The probabilities are recomputed from q and k; nothing of the forward is needed.
+ *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward (x_strides[3] =
+ *   {batch, head, row} in floats, d contiguous, 16-byte aligned, strides multiples of 4 floats); d in {32, 64}; 1 <= Lk <= 256.
+ *   dq (Lq, B, heads * d), dk / dv (Lk, B, heads * d): contiguous outputs.
+ * One workgroup per (batch entry, head) walks the queries in chunks of 16 in ascending order, so the sums of dK / dV over the
+ * queries have one fixed order and the bits of a (batch entry, head) do not depend on B.  No workspace.
+ */
+int dvis_attention_backward(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
+                            const float *v, const int64_t *v_strides, const float *grad_out, const int64_t *g_strides,
+                            float *dq, float *dk, float *dv, int B, int heads, int Lq, int Lk, int d, float scale,
+                            void *stream);
 
 /*
  * out[r, :] = LayerNorm(x[r, :] + res[r, :]) * gamma + beta, rows x C fp32 (C % 4 == 0, C <= 1024); `res` may be NULL
