@@ -1083,6 +1083,62 @@ DVIS_EXPORT int64_t dvis_attention_ws_bytes(int BH, int Lq, int Lk, int d) {
   return (int64_t)BH * ns * Lq * (d + 2) * (int64_t)sizeof(float);
 }
 
+// THE dispatch: which kernel serves a call and how its work is cut — the one place that decides it.  attention_launch acts on the
+// result and dvis_attention_plan reports it, so what a test is told cannot drift from what runs.
+//   served_by            DVIS_ATTN_* (include/dvis_hip.h)
+//   nsplit               key ranges per (batch, head) whose partials attn_combine_kernel merges (1: no merge)
+//   keys_per_split       keys of every split but the last, which holds Lk - (nsplit - 1) * keys_per_split
+//   qchunks              workgroups (key-partitioned kernel: waves) along the queries: of 128 queries (query-partitioned, split-f16 at
+//                        one query tile per wave), 16 (short kernel), 16 * kQT = 112 (key-partitioned)
+struct AttnPlan {
+  int served_by, nsplit, keys_per_split, qchunks;
+};
+
+static int attn_x3_qt() {
+  static const int qt = []() { const char *e = getenv("DVIS_ATTN_X3_QT"); return e ? atoi(e) : 1; }();     // (development)
+  return qt == 2 ? 2 : 1;
+}
+
+static int attention_decide(int BH, int Lq, int Lk, int d, bool has_mask, int64_t k_row, int64_t v_row, int kernel, AttnPlan *plan) {
+  DVIS_REQUIRE(BH > 0 && Lq > 0 && Lk > 0, "attention: bad sizes");
+  DVIS_REQUIRE(d == 32 || d == 64, "attention: head dim must be 32 or 64 (got %d)", d);
+  DVIS_REQUIRE(BH <= 65535, "attention: batch*heads must be <= 65535");
+  DVIS_REQUIRE(kernel == 0 || kernel == 2 || (kernel == 1 && Lk <= 128), "attention: kernel 1 (short keys) needs Lk <= 128 (Lk=%d)", Lk);
+  if (kernel == 2) {      // split-f16 long self-attention (ViT blocks): d = 64, no mask, enough query chunks that keys need no split
+    DVIS_REQUIRE(d == 64 && !has_mask && Lk >= 128, "attention: kernel 2 (split-f16) serves d = 64 without a mask, Lk >= 128");
+    const int qb = 128 * attn_x3_qt();
+    *plan = AttnPlan{DVIS_ATTN_X3, 1, Lk, (Lq + qb - 1) / qb};
+    return DVIS_OK;
+  }
+  if (kernel == 0 && keysplit_applies(Lq, Lk, d, has_mask, k_row, v_row)) {
+    const KeySplitPlan kp = plan_keysplit(BH, Lq, Lk);
+    *plan = AttnPlan{DVIS_ATTN_KEYSPLIT, kp.nsplit, kp.keys_per_split, kp.qchunks};
+    return DVIS_OK;
+  }
+  const SplitPlan p = plan_split(BH, Lq, Lk);
+  // Lk <= 128 (decoder / tracker / refiner self- and cross-attention over queries or frames): one workgroup per (batch, head,
+  // 16-query tile) with the keys split over 4 waves (8.0 vs 14.8 us for the tracker's batch-1 call) — for EVERY batch size: the
+  // kernels differ in their summation order, and choosing between them by the number of (batch, head) pairs (rounds 1 - 4: <= 384
+  // workgroups; at B = 30 the other kernel is 6 us faster per call) made a frame's bits depend on its batch mates.
+  // DVIS_ATTN_SHORT_MAX (development): the old rule.
+  static const long long short_max = []() { const char *e = getenv("DVIS_ATTN_SHORT_MAX"); return e ? atoll(e) : -1ll; }();
+  if (kernel == 1 || (Lk <= 128 && p.nsplit == 1 && (short_max < 0 || (long long)BH * ((Lq + 15) / 16) <= short_max))) {
+    *plan = AttnPlan{DVIS_ATTN_SHORT, 1, Lk, (Lq + 15) / 16};
+    return DVIS_OK;
+  }
+  *plan = AttnPlan{DVIS_ATTN_FWD, p.nsplit, p.keys_per_split, p.qchunks};
+  return DVIS_OK;
+}
+
+DVIS_EXPORT int dvis_attention_plan(int BH, int Lq, int Lk, int d, int has_mask, int64_t k_row, int64_t v_row, int kernel,
+                                    int32_t *plan) {
+  DVIS_REQUIRE(plan != nullptr, "attention_plan: null pointer");
+  AttnPlan p;
+  if (const int rc = attention_decide(BH, Lq, Lk, d, has_mask != 0, k_row, v_row, kernel, &p)) return rc;
+  plan[0] = p.served_by, plan[1] = p.nsplit, plan[2] = p.keys_per_split, plan[3] = p.qchunks;
+  return DVIS_OK;
+}
+
 static int attention_launch(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
                             const float *v, const int64_t *v_strides, float *out, const int64_t *o_strides,
                             const uint8_t *mask, const int32_t *allowed_count, int B, int heads, int Lq, int Lk, int d,
@@ -1090,9 +1146,9 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
   DVIS_REQUIRE(B >= 0 && heads > 0 && Lq >= 0 && Lk > 0, "attention: bad sizes");
   if (B == 0 || Lq == 0) return DVIS_OK;
   DVIS_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attention: null pointer");
-  DVIS_REQUIRE(d == 32 || d == 64, "attention: head dim must be 32 or 64 (got %d)", d);
   const int BH = B * heads;
-  DVIS_REQUIRE(BH <= 65535, "attention: batch*heads must be <= 65535");
+  AttnPlan plan;
+  if (const int rc = attention_decide(BH, Lq, Lk, d, mask != nullptr, k_strides[2], v_strides[2], kernel, &plan)) return rc;
   const dvis_strides qs{q_strides[0], q_strides[1], q_strides[2]}, ks{k_strides[0], k_strides[1], k_strides[2]};
   const dvis_strides vs{v_strides[0], v_strides[1], v_strides[2]}, os{o_strides[0], o_strides[1], o_strides[2]};
   const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v;
@@ -1100,27 +1156,23 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
                "attention: q/k/v must be 16-byte aligned with strides that are multiples of 4 floats");
   DVIS_REQUIRE(mask == nullptr || ((uintptr_t)mask & 3) == 0, "attention: mask must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  DVIS_REQUIRE(kernel == 0 || kernel == 2 || (kernel == 1 && Lk <= 128), "attention: kernel 1 (short keys) needs Lk <= 128 (Lk=%d)", Lk);
-  if (kernel == 2) {      // split-f16 long self-attention (ViT blocks): d = 64, no mask, enough query chunks that keys need no split
-    DVIS_REQUIRE(d == 64 && mask == nullptr && Lk >= 128, "attention: kernel 2 (split-f16) serves d = 64 without a mask, Lk >= 128");
+  if (plan.served_by == DVIS_ATTN_X3) {
     DVIS_REQUIRE(ws != nullptr, "attention: kernel 2 needs its workspace (dvis_attention_ws_bytes_k)");
     const X3Guard gd = dvis_x3_guard();
     _Float16 *wsh = (_Float16 *)ws;
     hipLaunchKernelGGL(attn_x3_pack_kernel, dim3((std::max(Lq, Lk) + 31) / 32, BH, 3), dim3(256), 0, st, q, qs, k, ks, v, vs, wsh, heads, Lq,
                        Lk, scale * kLog2e * 16.f);
     if (const int rc = dvis_check_launch("attn_x3_pack_kernel")) return rc;
-    static const int qt = []() { const char *e = getenv("DVIS_ATTN_X3_QT"); return e ? atoi(e) : 1; }();     // (development)
-    if (qt == 2)
-      hipLaunchKernelGGL(attn_x3_kernel<2>, dim3(((BH + 7) / 8) * 8 * ((Lq + 255) / 256)), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
+    if (attn_x3_qt() == 2)
+      hipLaunchKernelGGL(attn_x3_kernel<2>, dim3(((BH + 7) / 8) * 8 * plan.qchunks), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
                          gd.flag, gd.tag);
     else
-      hipLaunchKernelGGL(attn_x3_kernel<1>, dim3(((BH + 7) / 8) * 8 * ((Lq + 127) / 128)), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
+      hipLaunchKernelGGL(attn_x3_kernel<1>, dim3(((BH + 7) / 8) * 8 * plan.qchunks), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
                          gd.flag, gd.tag);
     return dvis_check_launch("attn_x3_kernel");
   }
-  kernel = kernel == 1 ? 1 : 0;
-  if (kernel == 0 && keysplit_applies(Lq, Lk, d, mask != nullptr, ks.r, vs.r)) {
-    const KeySplitPlan kp = plan_keysplit(BH, Lq, Lk);
+  if (plan.served_by == DVIS_ATTN_KEYSPLIT) {
+    const AttnPlan &kp = plan;
     DVIS_REQUIRE(kp.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes)");
     float *kws_o = (float *)ws;
     float *kws_ml = kws_o ? kws_o + (size_t)BH * kp.nsplit * Lq * d : nullptr;
@@ -1135,19 +1187,8 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
                        Lq, d, heads, total, out, os);
     return dvis_check_launch("attn_combine_kernel");
   }
-  const SplitPlan p = plan_split(BH, Lq, Lk);
-  DVIS_REQUIRE(p.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes)");
-  float *ws_o = (float *)ws;
-  float *ws_ml = ws_o ? ws_o + (size_t)BH * p.nsplit * Lq * d : nullptr;
-  const dim3 grid(p.nsplit, BH, p.qchunks), block(512);
-// Lk <= 128 (decoder / tracker / refiner self- and cross-attention over queries or frames): one workgroup per (batch, head,
-  // 16-query tile) with the keys split over 4 waves (8.0 vs 14.8 us for the tracker's batch-1 call) — for EVERY batch size: the
-  // kernels differ in their summation order, and choosing between them by the number of (batch, head) pairs (rounds 1 - 4: <= 384
-  // workgroups; at B = 30 the other kernel is 6 us faster per call) made a frame's bits depend on its batch mates.
-  // DVIS_ATTN_SHORT_MAX (development): the old rule.
-  static const long long short_max = []() { const char *e = getenv("DVIS_ATTN_SHORT_MAX"); return e ? atoll(e) : -1ll; }();
-  if (kernel == 1 || (Lk <= 128 && p.nsplit == 1 && (short_max < 0 || (long long)BH * ((Lq + 15) / 16) <= short_max))) {
-    const dim3 sgrid((Lq + 15) / 16, BH);
+  if (plan.served_by == DVIS_ATTN_SHORT) {
+    const dim3 sgrid(plan.qchunks, BH);
     const int nrows = (Lk + 15) / 16 * 16, ls = d + 4;
     const size_t lds = sizeof(float) * ((size_t)std::max(nrows * ls, 64 * d) + (size_t)nrows * ls + 128);
     static DvisLdsOptIn opted32, opted64;       // (d = 64 with 113 .. 128 keys needs 70 KB)
@@ -1162,7 +1203,12 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
                          heads, Lq, Lk, scale);
     return dvis_check_launch("attn_short_kernel");
   }
-  #define DVIS_ATTN(DH_, SHORT_)                                                                                     \
+  const AttnPlan &p = plan;      // DVIS_ATTN_FWD
+  DVIS_REQUIRE(p.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes)");
+  float *ws_o = (float *)ws;
+  float *ws_ml = ws_o ? ws_o + (size_t)BH * p.nsplit * Lq * d : nullptr;
+  const dim3 grid(p.nsplit, BH, p.qchunks), block(512);
+  #define DVIS_ATTN(DH_, SHORT_)                                                                                    \
   hipLaunchKernelGGL((attn_fwd_kernel<DH_, SHORT_>), grid, block, 0, st, q, qs, k, ks, v, vs, out, os, mask, allowed_count, \
                      heads, Lq, Lk, scale, p.nsplit, p.keys_per_split, ws_o, ws_ml)
   const bool shrt = Lk <= 128 && p.nsplit == 1;

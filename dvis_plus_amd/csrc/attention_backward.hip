@@ -97,26 +97,31 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     }
     __syncthreads();
 
-    // ---- (2) this key's column: s = q_i . k_t (log2 units), dp = dO_i . v_t.  (The loop over the rows stays rolled: unrolled,
-    // hipcc issues the LDS reads of all 16 rows first and spills a thousand registers.)
+    // ---- (2) this key's column: s = q_i . k_t (log2 units), dp = dO_i . v_t.  Each dot product runs as FOUR fma chains, one per
+    // component of the float4 pieces (dims c, c + 4, c + 8, ...), summed pairwise at the end: a single chain over d = 64 unscaled
+    // products carried 4 - 8 times the rounding error of a blocked fp32 dot product into the scores (with one query nothing
+    // averages it out of dv = p dO: 4.8e-07 against 1.1e-07 of an fp32 CPU run at Lq 1, Lk 17, d 64), and four independent
+    // chains are four times shorter on the fma latency.  (The loop over the rows stays rolled: unrolled, hipcc issues the LDS
+    // reads of all 16 rows first and spills a thousand registers.)
 #pragma unroll 1
     for (int i = 0; key_on && i < kQC; ++i) {
-      float s = 0.f, dp = 0.f;
+      float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = s4;
 #pragma unroll
       for (int c = 0; c < C4; ++c) {
         const float4 kk = *reinterpret_cast<const float4 *>(krow + 4 * c);
         const float4 vv = vr[c];
         const float4 qq = *reinterpret_cast<const float4 *>(&q_lds[i * LS + 4 * c]);
         const float4 gg = *reinterpret_cast<const float4 *>(&g_lds[i * LS + 4 * c]);
-        s = fmaf(qq.x, kk.x, s);
-        s = fmaf(qq.y, kk.y, s);
-        s = fmaf(qq.z, kk.z, s);
-        s = fmaf(qq.w, kk.w, s);
-        dp = fmaf(gg.x, vv.x, dp);
-        dp = fmaf(gg.y, vv.y, dp);
-        dp = fmaf(gg.z, vv.z, dp);
-        dp = fmaf(gg.w, vv.w, dp);
+        s4.x = fmaf(qq.x, kk.x, s4.x);
+        s4.y = fmaf(qq.y, kk.y, s4.y);
+        s4.z = fmaf(qq.z, kk.z, s4.z);
+        s4.w = fmaf(qq.w, kk.w, s4.w);
+        d4.x = fmaf(gg.x, vv.x, d4.x);
+        d4.y = fmaf(gg.y, vv.y, d4.y);
+        d4.z = fmaf(gg.z, vv.z, d4.z);
+        d4.w = fmaf(gg.w, vv.w, d4.w);
       }
+      const float s = (s4.x + s4.y) + (s4.z + s4.w), dp = (d4.x + d4.y) + (d4.z + d4.w);
       s_lds[i * SS + tid] = s * sl2;
       p_lds[i * SS + tid] = dp;
     }
@@ -199,6 +204,13 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
 
 }  // namespace
 
+// Threads per workgroup: one per key, rounded up to 64 / 128 / 256 — a function of Lk alone (see "determinism" above).  The launch
+// takes its block size from here; tests ask the same function which geometry a case runs at.
+DVIS_EXPORT int dvis_attention_backward_threads(int Lk) {
+  if (Lk < 1 || Lk > kMaxLk) return 0;
+  return Lk <= 64 ? 64 : Lk <= 128 ? 128 : 256;
+}
+
 DVIS_EXPORT int dvis_attention_backward(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
                                         const float *v, const int64_t *v_strides, const float *grad_out, const int64_t *g_strides,
                                         float *dq, float *dk, float *dv, int B, int heads, int Lq, int Lk, int d, float scale,
@@ -221,7 +233,7 @@ DVIS_EXPORT int dvis_attention_backward(const float *q, const int64_t *q_strides
   if (const int rc = d == 32 ? dvis_lds_opt_in((const void *)attn_bwd_kernel<32>, lds, &opted32, "attn_bwd_kernel")
                              : dvis_lds_opt_in((const void *)attn_bwd_kernel<64>, lds, &opted64, "attn_bwd_kernel"))
     return rc;
-  const int threads = Lk <= 64 ? 64 : Lk <= 128 ? 128 : 256;
+  const int threads = dvis_attention_backward_threads(Lk);
   hipStream_t st = (hipStream_t)stream;
   if (d == 32)
     hipLaunchKernelGGL((attn_bwd_kernel<32>), dim3((unsigned)(B * heads)), dim3(threads), lds, st, q, qs, k, ks, v, vs, grad_out, gs,

@@ -9,6 +9,7 @@ unchanged.  Differences, all deliberate:
   * fp16 / bf16 tensors are accepted in forward (fp32 accumulation) besides float / double,
   * failures raise ``RuntimeError`` — there is no torch/CPU fallback to hide them.
 """
+import collections
 import ctypes
 import math
 import os
@@ -510,6 +511,38 @@ def attention(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=Fa
     return _attention_kernel(q, k, v, nheads, mask, allowed_count, out, short)
 
 
+def _attention_kernel_arg(Lq, Lk, d, has_mask, short):
+    """The `kernel` argument of dvis_attention_forward_k for a call: 1 = the pinned short-key kernel, 2 = split-f16, 0 = the library's
+    own choice from the sizes."""
+    if short:
+        return 1
+    if not has_mask and d == 64 and Lq >= 1024 and Lk >= 1024 and x3_on():
+        # long self-attention at head dim 64 (the DINOv2 / ViT-Adapter blocks: 3681 tokens x 16 heads): split-f16 matrix-core kernel
+        return 2
+    return 0
+
+
+ATTENTION_KERNELS = ("attn_fwd_kernel", "attn_short_kernel", "attn_x3_kernel", "attn_keysplit_kernel")      # DVIS_ATTN_* of dvis_hip.h
+AttentionPlan = collections.namedtuple("AttentionPlan", "kernel nsplit keys_per_split qchunks")
+
+
+def attention_plan(q, k, nheads, mask=None, short=False):
+    """What ``attention(q, k, v, nheads, mask, short=short)`` would launch (v shaped and strided like k), without launching it:
+    AttentionPlan(kernel, nsplit, keys_per_split, qchunks) — the kernel's name (ATTENTION_KERNELS), the number of key ranges whose
+    partial results a second launch merges, the keys of each but the last (which holds Lk - (nsplit - 1) * keys_per_split) and the
+    number of units along the queries (128 queries each on attn_fwd_kernel / attn_x3_kernel, 112 on attn_keysplit_kernel, 16 on
+    attn_short_kernel).  The answer comes from dvis_attention_plan, the function the launch itself consults, after this module's
+    own split-f16 rule; only shapes and strides are read, so CPU tensors are fine."""
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    d = C // nheads
+    plan = (ctypes.c_int32 * 4)()
+    rc = native.lib().dvis_attention_plan(B * nheads, Lq, Lk, d, int(mask is not None), k.stride(0), k.stride(0),
+                                          _attention_kernel_arg(Lq, Lk, d, mask is not None, short), plan)
+    native.check(rc, "dvis_attention_plan")
+    return AttentionPlan(ATTENTION_KERNELS[plan[0]], plan[1], plan[2], plan[3])
+
+
 def _attention_kernel(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=False):
     Lq, B, C = q.shape
     Lk = k.shape[0]
@@ -533,10 +566,8 @@ def _attention_kernel(q, k, v, nheads, mask=None, allowed_count=None, out=None, 
                 raise RuntimeError("attention: allowed_count must be int32 (B, Lq)")
             aptr = native.dev_ptr(allowed_count, "allowed_count")
     lib = native.lib()
-    kern = 1 if short else 0
-    if not short and mask is None and d == 64 and Lq >= 1024 and Lk >= 1024 and x3_on():
-        # long self-attention at head dim 64 (the DINOv2 / ViT-Adapter blocks: 3681 tokens x 16 heads): split-f16 matrix-core kernel
-        kern = 2
+    kern = _attention_kernel_arg(Lq, Lk, d, mask is not None, short)
+    if kern == 2:
         X3_GUARD.word(q.device)          # (its range guard reports under the tag of the last packed weight: the block's qkv)
     nbytes = lib.dvis_attention_ws_bytes_k(B * nheads, Lq, Lk, d, kern)
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=q.device) if nbytes else None
@@ -598,6 +629,15 @@ def attention_backward(q, k, v, grad_out, nheads):
             _strides3(grad_out, B, C, d), ptr(dq), ptr(dk), ptr(dv), B, nheads, Lq, Lk, d, 1.0 / (d ** 0.5), native.stream_ptr(dev))
     native.check(rc, "dvis_attention_backward")
     return dq, dk, dv
+
+
+def attention_backward_threads(Lk):
+    """Threads per workgroup ``attention_backward`` launches for Lk keys (64, 128 or 256: 4, 8 or 16 lanes per query row in the row
+    reductions) — asked of the library, whose launch uses the same function."""
+    n = native.lib().dvis_attention_backward_threads(int(Lk))
+    if n <= 0:
+        raise RuntimeError(f"attention_backward: serves 1 .. {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
+    return n
 
 
 class AttentionFunction(Function):

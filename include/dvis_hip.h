@@ -275,6 +275,20 @@ int dvis_attention_forward_k(const float *q, const int64_t *q_strides, const flo
  * take in fp32), then one workgroup per (batch-head, 128 queries) streams K / V from there.  Operands must stay below 4095 (65520 / 2^4) in
  * magnitude (the range guard of dvis_x3_set_range_flag reports a violation). */
 int64_t dvis_attention_ws_bytes_k(int BH, int Lq, int Lk, int d, int kernel);
+/* Which kernel dvis_attention_forward_k(.., kernel) would launch for these sizes and how it cuts the work — host only, nothing is
+ * launched; the launch takes its decision from the same function, so the answer is the dispatch and not a description of it.
+ *   k_row / v_row: row strides of k / v in floats (x_strides[2]); has_mask: mask != NULL.
+ *   plan[4] = {served_by (DVIS_ATTN_*), nsplit, keys_per_split, qchunks}: nsplit key ranges of keys_per_split keys per (batch, head)
+ *   (the last holds Lk - (nsplit - 1) * keys_per_split; partials merged by a second launch when nsplit > 1), qchunks units along the
+ *   queries: of 128 queries (DVIS_ATTN_FWD, DVIS_ATTN_X3), 112 (DVIS_ATTN_KEYSPLIT) or 16 (DVIS_ATTN_SHORT).
+ * Refuses what the launch refuses for the same arguments (head dim, batch * heads, kernel 1 with Lk > 128, kernel 2 with a mask...). */
+enum {
+  DVIS_ATTN_FWD = 0,      /* attn_fwd_kernel: query-partitioned, keys in LDS stages, optional split over keys */
+  DVIS_ATTN_SHORT = 1,    /* attn_short_kernel: Lk <= 128, one workgroup per 16 queries, keys over 4 waves */
+  DVIS_ATTN_X3 = 2,       /* attn_x3_kernel: split-f16 products, d = 64, no mask (kernel = 2 only) */
+  DVIS_ATTN_KEYSPLIT = 3  /* attn_keysplit_kernel: d = 32, > 64 queries, >= 512 keys, one key range per wave */
+};
+int dvis_attention_plan(int BH, int Lq, int Lk, int d, int has_mask, int64_t k_row, int64_t v_row, int kernel, int32_t *plan);
 
 /*
  * Backward of softmax(Q K^T * scale) V without a mask, fp32, exact fp32 FMA arithmetic, deterministic (no float atomics):
@@ -291,6 +305,9 @@ int dvis_attention_backward(const float *q, const int64_t *q_strides, const floa
                             const float *v, const int64_t *v_strides, const float *grad_out, const int64_t *g_strides,
                             float *dq, float *dk, float *dv, int B, int heads, int Lq, int Lk, int d, float scale,
                             void *stream);
+/* Threads per workgroup of that launch: 64, 128 or 256 (one per key; the row reductions then run over 4, 8 or 16 lanes per query row);
+ * 0 for an Lk the kernel does not serve.  Host only; the launch takes its block size from it. */
+int dvis_attention_backward_threads(int Lk);
 
 /*
  * out[r, :] = LayerNorm(x[r, :] + res[r, :]) * gamma + beta, rows x C fp32 (C % 4 == 0, C <= 1024); `res` may be NULL

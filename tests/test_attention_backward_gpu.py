@@ -10,11 +10,19 @@ with torch.exp2 on scores scaled by scale * log2(e).  It is never the kernel's o
 
 With q = 0 every probability is exactly 1 / Lk; at Lk = 16 and integer v / grad_out every product and sum is exact in fp32, so dv
 must be bit-equal to the fp64 result and dk must be zero whatever the order: indexing and chunk-edge errors show without a
-tolerance."""
+tolerance.
+
+The lattice walks the launch geometry (64 / 128 / 256 threads = 4 / 8 / 16 reduction lanes per query row, asserted through
+functions.attention_backward_threads) and the 16-query chunk edge at both head dims.  One-hot attention (inputs of
+tests/test_attention_edges_gpu.py: a target key per query that leads its row by >= 200 log2 units) makes dq and dk exactly zero and
+dv an exact integer sum; rows whose maxima run from -900 to +900 log2 units need the max subtraction in front of the exponential.
+Both assert their precondition on the CPU before the GPU is touched."""
 import math
 
 import pytest
 import torch
+
+from test_attention_edges_gpu import assert_score_range, one_hot_inputs, one_hot_margin, score_range_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -198,3 +206,95 @@ def test_refusals_are_host_side(Fn):
         Fn.attention_backward(z(4), z(4), z(4, dtype=torch.float64), z(4), heads)
     with pytest.raises(RuntimeError, match="inner stride"):
         Fn.attention_backward(z(4, 2 * C)[..., ::2], z(4), z(4), z(4), heads)
+
+
+# Lk -> threads of the launch (one per key, rounded up to 64 / 128 / 256; R = threads / 16 lanes reduce a query row): the switches at
+# 64 / 65 and 128 / 129, Lk below R (2, 3: reduction lanes that own no key), Lk around the 16-key granule of nothing in particular
+# (15 / 16 / 17 — the kernel has no key tile, so these must not matter), the limit 256.
+LATTICE_LK = {2: 64, 3: 64, 15: 64, 16: 64, 17: 64, 63: 64, 64: 64, 65: 128, 127: 128, 128: 128, 129: 256, 255: 256, 256: 256}
+LATTICE_LQ = [1, 15, 16, 17, 33]          # the 16-query chunk: below, at, one past, two chunks + 1
+
+
+def _check_against_fp64(Fn, q, k, v, go, heads, label):
+    """The file's yardstick on one set of inputs: every tensor within 4 x the worse fp32 CPU formulation's error against fp64
+    autograd.  A tensor whose fp32 CPU error is 0 (its exact gradient is 0) takes the largest fp32 CPU error of the three as baseline."""
+    ref, base = _bounds(q, k, v, go, heads)
+    base = [b if b > 0 else max(base) for b in base]
+    got = Fn.attention_backward(*(t.cuda() for t in (q, k, v, go)), heads)
+    errs = []
+    for name, x, r, b in zip(("dq", "dk", "dv"), got, ref, base):
+        assert x.shape == r.shape and x.dtype == torch.float32 and x.is_contiguous() and r.numel() >= 64
+        err = (x.cpu().double() - r).abs().max().item()
+        errs.append(err)
+        print(f"{label} {name}: err {err:.3e} fp32 CPU err {b:.3e} ratio {err / b:.2f}")
+    for name, err, b in zip(("dq", "dk", "dv"), errs, base):
+        assert err <= 4 * b, f"{label} {name}: err {err:.3e} > 4 x {b:.3e}"          # (NaN fails)
+    return got
+
+
+@pytest.mark.parametrize("d", [32, 64])
+@pytest.mark.parametrize("Lk", sorted(LATTICE_LK))
+def test_backward_lattice_of_thread_counts_and_chunk_edges(Fn, Lk, d):
+    """B = 2, heads = 2: every compared tensor has at least 128 elements.
+
+    Lq = 1 is the sharpest row of the lattice: dv = p x grad_out of a single query averages nothing, so the rounding of the scores
+    shows undiluted.  With q . k as ONE fma chain over the head dim the kernel missed the bound here (Lk 17, d 64, dv: 4.759e-07
+    against an fp32 CPU figure of 1.145e-07, ratio 4.16); the kernel now sums four chains pairwise (2.394e-07, ratio 2.09)."""
+    assert Fn.attention_backward_threads(Lk) == LATTICE_LK[Lk]
+    B, heads = 2, 2
+    for Lq in LATTICE_LQ:
+        q, k, v, go = _draw(Lq, Lk, B, heads, d, 31 + Lq)
+        _check_against_fp64(Fn, q, k, v, go, heads, f"lattice {(Lq, Lk, B, heads, d)}")
+
+
+@pytest.mark.parametrize("Lq,Lk,d", [(33, 256, 64), (100, 100, 32)])
+def test_one_hot_attention_gradients_are_exact(Fn, Lq, Lk, d):
+    """Every probability is exactly 0 or 1: dS = P o (dP - D) is exactly 0, so dq == dk == 0, and dv[t] is the integer sum of the
+    grad_out rows whose query chose t (several queries share a key, most keys are chosen by none)."""
+    B, heads = 2, 2
+    q, k, v, pi = one_hot_inputs(Lq, Lk, d, 41 + Lq, integer_v=True)
+    go = torch.randint(-3, 4, (Lq, B, heads * d), generator=torch.Generator().manual_seed(42)).float()
+    assert one_hot_margin(q, k, d, pi) >= 200.0
+    want_dv = torch.zeros(Lk, B, heads * d)
+    for b in range(B):
+        want_dv[:, b].index_add_(0, pi[b], go[:, b])
+    assert any(pi[b].unique().numel() < Lq for b in range(B))
+    cq, ck, cv = _cpu_grads(q, k, v, go, heads, torch.float32)
+    assert (cq == 0).all() and (ck == 0).all() and torch.equal(cv, want_dv)       # the reference alone meets the claim
+    dq, dk, dv = (t.cpu() for t in Fn.attention_backward(q.cuda(), k.cuda(), v.cuda(), go.cuda(), heads))
+    assert (dq == 0).all() and (dk == 0).all()
+    assert torch.equal(dv, want_dv)
+
+
+# one case per launch geometry
+RANGE_SHAPES = [(20, 40, 32), (33, 100, 32), (17, 256, 64)]
+
+
+@pytest.mark.parametrize("Lq,Lk,d", RANGE_SHAPES)
+def test_backward_with_row_maxima_from_minus_900_to_plus_900_log2_units(Fn, Lq, Lk, d):
+    """Without the subtraction of the row maximum 2^s overflows for the rows near +900 and underflows to l = 0 for those near -900.
+    Bound: the file's measured 4 x e32 per tensor; a tensor whose fp32 CPU error is 0 because its exact gradient is 0 would take the
+    largest fp32 CPU error among the three tensors as its baseline (the per-parameter check of tests/test_refiner_train_gpu.py sets
+    the precedent)."""
+    heads = 2
+    q, k, v = score_range_inputs(Lq, Lk, d, 51 + Lk)
+    go = torch.randn(q.shape, generator=torch.Generator().manual_seed(52))
+    assert_score_range(q, k, d)
+    _check_against_fp64(Fn, q, k, v, go, heads, f"score range {(Lq, Lk, d)}")
+
+
+def test_autograd_over_the_score_range(Fn):
+    Lq, Lk, d = RANGE_SHAPES[1]
+    heads = 2
+    q, k, v = (t.cuda() for t in score_range_inputs(Lq, Lk, d, 53))
+    go = torch.randn(q.shape, generator=torch.Generator().manual_seed(54)).cuda()
+    assert_score_range(q.cpu(), k.cpu(), d)
+    with torch.no_grad():
+        plain = Fn.attention(q, k, v, heads)
+    assert torch.isfinite(plain).all()
+    leaves = [t.clone().requires_grad_() for t in (q, k, v)]
+    out = Fn.attention(*leaves, heads)
+    assert out.requires_grad and torch.equal(out.detach(), plain)
+    grads = torch.autograd.grad(out, leaves, go)
+    want = Fn.attention_backward(q, k, v, go, heads)
+    assert all(torch.equal(g, w) for g, w in zip(grads, want))

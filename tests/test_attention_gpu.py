@@ -23,24 +23,32 @@ def ref_attention(q, k, v, nheads, mask=None):
     return o.permute(2, 0, 1, 3).reshape(Lq, B, C)
 
 
-CASES = [  # (Lq, Lk, B, heads, d, masked)
-    (100, 920, 2, 8, 32, True), (100, 3680, 2, 8, 32, True), (100, 14720, 1, 8, 32, True),
-    (100, 100, 3, 8, 64, False), (30, 30, 100, 8, 64, False), (100, 100, 30, 8, 64, False),
-    (6, 24, 2, 2, 32, True), (6, 6, 1, 2, 32, False), (200, 333, 2, 8, 32, True), (17, 70, 2, 4, 64, True),
-    (5, 5, 6, 2, 32, False), (130, 257, 1, 2, 64, True),
-    # few (batch, head, query-tile) workgroups and Lk <= 128: the key-split latency kernel (tracker shapes)
-    (100, 100, 1, 8, 64, True), (100, 100, 1, 8, 32, True), (100, 128, 1, 8, 64, True), (33, 113, 2, 4, 32, True),
-    (100, 1, 1, 8, 64, False), (1, 100, 1, 8, 64, False),
-    # key-partitioned kernel (d = 32, > 64 queries, >= 512 keys): two query chunks, ragged last key tile, 65 queries
-    # (one live row in the fifth tile), no mask with Lk % 4 != 0, many (batch, head) pairs (one split per wave)
-    (200, 1000, 2, 8, 32, True), (65, 516, 1, 4, 32, True), (100, 777, 2, 8, 32, False), (112, 2000, 1, 2, 32, False),
-    (100, 640, 40, 8, 32, True), (113, 530, 3, 8, 32, True),
+# (cases (Lq, Lk, B, heads, d, masked), the kernel functions.attention_plan must report for each of them): the labels are asserted, so a
+# moved dispatch threshold fails here instead of quietly moving a case to another kernel
+CASE_GROUPS = [
+    # decoder cross-attention levels of the R50 benchmark: the key-partitioned kernel (d = 32, > 64 queries, >= 512 keys)
+    ([(100, 920, 2, 8, 32, True), (100, 3680, 2, 8, 32, True), (100, 14720, 1, 8, 32, True)], "attn_keysplit_kernel"),
+    # Lk <= 128: the short-key latency kernel at every batch size (tracker / refiner / decoder self-attention shapes)
+    ([(100, 100, 3, 8, 64, False), (30, 30, 100, 8, 64, False), (100, 100, 30, 8, 64, False), (6, 24, 2, 2, 32, True),
+      (6, 6, 1, 2, 32, False), (17, 70, 2, 4, 64, True), (5, 5, 6, 2, 32, False),
+      (100, 100, 1, 8, 64, True), (100, 100, 1, 8, 32, True), (100, 128, 1, 8, 64, True), (33, 113, 2, 4, 32, True),
+      (100, 1, 1, 8, 64, False), (1, 100, 1, 8, 64, False)], "attn_short_kernel"),
+    # query-partitioned kernel: 129 .. 511 keys, d = 64 at any length — and d = 32 with a mask whose rows are not 4-byte aligned
+    # (Lk % 4 != 0), whatever Lq and Lk: (113, 530) is that case, split over keys, two query chunks with one live row in the second
+    ([(200, 333, 2, 8, 32, True), (130, 257, 1, 2, 64, True), (113, 530, 3, 8, 32, True)], "attn_fwd_kernel"),
+    # key-partitioned kernel (d = 32, > 64 queries, >= 512 keys, a mask only with Lk % 4 == 0): two query chunks, ragged last key
+    # tile, 65 queries (one live row in the fifth tile), no mask with Lk % 4 != 0, many (batch, head) pairs (one split per wave),
+    # 113 queries = 7 tiles + one live row in a second query chunk under a mask
+    ([(200, 1000, 2, 8, 32, True), (65, 516, 1, 4, 32, True), (100, 777, 2, 8, 32, False), (112, 2000, 1, 2, 32, False),
+      (100, 640, 40, 8, 32, True), (113, 532, 3, 8, 32, True)], "attn_keysplit_kernel"),
 ]
+CASES = [case for cases, _ in CASE_GROUPS for case in cases]
+EXPECTED_KERNEL = {case: kernel for cases, kernel in CASE_GROUPS for case in cases}
 
 
 @pytest.mark.parametrize("Lq,Lk,B,H,d,masked", CASES)
 def test_attention_vs_fp64(Lq, Lk, B, H, d, masked):
-    from dvis_plus_amd.functions import attention
+    from dvis_plus_amd.functions import attention, attention_plan
     g = torch.Generator().manual_seed(Lq * 7 + Lk)
     C = H * d
     q, k, v = (torch.randn(L, B, C, generator=g) for L in (Lq, Lk, Lk))
@@ -50,6 +58,7 @@ def test_attention_vs_fp64(Lq, Lk, B, H, d, masked):
         mask = torch.rand(B, Lq, Lk, generator=g) < 0.7
         mask[:, :, 0] = False                      # every row keeps at least one key
         mask[0, 0, 1:] = True                      # a row with exactly one live key
+    assert attention_plan(q, k, H, mask).kernel == EXPECTED_KERNEL[(Lq, Lk, B, H, d, masked)]
     ref = ref_attention(q, k, v, H, mask)
     out = attention(q.to(DEV), k.to(DEV), v.to(DEV), H, None if mask is None else mask.to(DEV)).cpu()
     torch.testing.assert_close(out.double(), ref, rtol=0, atol=2e-5)
