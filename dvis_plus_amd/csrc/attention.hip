@@ -50,7 +50,7 @@ struct SplitPlan {
 // result depends on where the splits fall, and a frame of the per-frame segmenter (frames = batch) must get the same bits
 // whether it is computed alone, in a 30-frame clip or in a rank's 4-frame shard (north_star's frame sharding).  (Rounds 1 - 4
 // sized the split from the number of (batch, head) pairs to fill the chip at every batch size: batch-dependent bits.)
-SplitPlan plan_split(int /*BH*/, int Lq, int Lk) {
+SplitPlan plan_split(int Lq, int Lk) {
   SplitPlan p;
   p.qchunks = (Lq + 127) / 128;
   int ns = (16 + p.qchunks - 1) / p.qchunks;            // >= 16 workgroups per (batch, head) from chunks x splits
@@ -63,7 +63,7 @@ SplitPlan plan_split(int /*BH*/, int Lq, int Lk) {
   return p;
 }
 
-template <int DH, bool SHORT>
+template <int DH>
 __global__ __launch_bounds__(512) void attn_fwd_kernel(
     const float *__restrict__ q, dvis_strides qs, const float *__restrict__ k, dvis_strides ks_, const float *__restrict__ v,
     dvis_strides vs, float *__restrict__ out, dvis_strides os, const uint8_t *__restrict__ mask,
@@ -72,13 +72,11 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(
   constexpr int DQ = DH / 4;        // dims per lane group
   constexpr int NT = DH / 16;       // output N tiles
   constexpr int LS = DH + 4;        // LDS row stride (floats): 16-B aligned, V rows of lane groups 0/1 split banks
-  // keys per LDS stage.  Long key sequences: 64 (d=32) / 32 (d=64) with a register prefetch of the next stage.
-  // (64 keys at d=64 was measured on the ViT-L shape — 3681 tokens, 16 heads: 17.83 ms either way, 93 TFLOP/s — so
-  // the smaller stage is kept for its 17 KB of LDS.  An earlier form of the prefetch — float4 arrays with a zero-fill
-  // branch — crashed hipcc 7.2's machine-copy-propagation pass at F4 = 2; the scalar form below compiles.)  SHORT (Lk <= 128: tracker / refiner / decoder self-attention): ONE 128-key stage written
-  // straight to LDS, so the whole call pays a single global-load latency instead of one per 32-key stage.
-  constexpr int KT = SHORT ? 128 : (DH == 64 ? 32 : 64);
-  constexpr int F4 = SHORT ? 1 : KT * DH / 4 / 512;   // float4 per thread per matrix per stage (prefetch registers)
+  // keys per LDS stage: 64 (d=32) / 32 (d=64) with a register prefetch of the next stage, one float4 per thread per
+  // matrix.  (64 keys at d=64 was measured on the ViT-L shape — 3681 tokens, 16 heads: 17.83 ms either way, 93 TFLOP/s —
+  // so the smaller stage is kept for its 17 KB of LDS.)  Lk <= 128 never comes here: attn_short_kernel serves it.
+  constexpr int KT = DH == 64 ? 32 : 64;
+  static_assert(KT * DH / 4 == 512, "one float4 per thread per matrix per stage");
   __shared__ float k_lds[KT * LS];
   __shared__ float v_lds[KT * LS];
 
@@ -119,58 +117,31 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(
 
   const float *kb = k + (size_t)bi * ks_.b + (size_t)hi * ks_.h;
   const float *vb = v + (size_t)bi * vs.b + (size_t)hi * vs.h;
-  // prefetch registers as scalars (F4 <= 2): as arrays captured by a lambda hipcc keeps them in scratch
-  static_assert(F4 == 1 || F4 == 2, "stage size");
-  float4 pk0, pv0, pk1, pv1;
-  pk0 = pv0 = pk1 = pv1 = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto stage_addr = [&](int i, int &row, int &c4) {
-    const int e = tid + 512 * i;                // float4 index within the stage
-    row = e / (DH / 4);
-    c4 = e - row * (DH / 4);
+  // prefetch registers as scalars: as arrays captured by a lambda hipcc keeps them in scratch
+  float4 pk0, pv0;
+  pk0 = pv0 = make_float4(0.f, 0.f, 0.f, 0.f);
+  auto stage_addr = [&](int &row, int &c4) {     // this thread's float4 within the stage (recomputed at each use, as before)
+    row = tid / (DH / 4);
+    c4 = tid - row * (DH / 4);
   };
   auto prefetch = [&](int ks) {
     // rows past the split's last key re-read that last key: they are masked out of the softmax below (p = 0 exactly)
     // and real rows are finite, so no zero fill / branch is needed
     int row, c4;
-    stage_addr(0, row, c4);
-    int key = min(ks + row, key_hi - 1);
+    stage_addr(row, c4);
+    const int key = min(ks + row, key_hi - 1);
     pk0 = *reinterpret_cast<const float4 *>(kb + (size_t)key * ks_.r + 4 * c4);
     pv0 = *reinterpret_cast<const float4 *>(vb + (size_t)key * vs.r + 4 * c4);
-    if (F4 > 1) {
-      stage_addr(1, row, c4);
-      key = min(ks + row, key_hi - 1);
-      pk1 = *reinterpret_cast<const float4 *>(kb + (size_t)key * ks_.r + 4 * c4);
-      pv1 = *reinterpret_cast<const float4 *>(vb + (size_t)key * vs.r + 4 * c4);
-    }
   };
-  if (!SHORT) prefetch(key_lo);
+  prefetch(key_lo);
   for (int ks = key_lo; ks < key_hi; ks += KT) {
     __syncthreads();
-    if (SHORT) {
-      for (int e = tid; e < KT * DH / 4; e += 512) {
-        const int row = e / (DH / 4), c4 = e - row * (DH / 4);
-        const int key = ks + row;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        if (key < key_hi) {
-          a = *reinterpret_cast<const float4 *>(kb + (size_t)key * ks_.r + 4 * c4);
-          b = *reinterpret_cast<const float4 *>(vb + (size_t)key * vs.r + 4 * c4);
-        }
-        *reinterpret_cast<float4 *>(&k_lds[row * LS + 4 * c4]) = a;
-        *reinterpret_cast<float4 *>(&v_lds[row * LS + 4 * c4]) = b;
-      }
-    } else {
-      int row, c4;
-      stage_addr(0, row, c4);
-      *reinterpret_cast<float4 *>(&k_lds[row * LS + 4 * c4]) = pk0;
-      *reinterpret_cast<float4 *>(&v_lds[row * LS + 4 * c4]) = pv0;
-      if (F4 > 1) {
-        stage_addr(1, row, c4);
-        *reinterpret_cast<float4 *>(&k_lds[row * LS + 4 * c4]) = pk1;
-        *reinterpret_cast<float4 *>(&v_lds[row * LS + 4 * c4]) = pv1;
-      }
-    }
+    int row, c4;
+    stage_addr(row, c4);
+    *reinterpret_cast<float4 *>(&k_lds[row * LS + 4 * c4]) = pk0;
+    *reinterpret_cast<float4 *>(&v_lds[row * LS + 4 * c4]) = pv0;
     __syncthreads();
-    if (!SHORT && ks + KT < key_hi) prefetch(ks + KT);
+    if (ks + KT < key_hi) prefetch(ks + KT);
     if (!wave_on) continue;
     // Software pipeline over the key tiles of the stage: the score MFMAs of tile kt + 1 are ISSUED before the softmax
     // VALU work of tile kt, so the matrix pipe executes them in the shadow of that VALU work (an MFMA is asynchronous;
@@ -324,13 +295,12 @@ constexpr int kQT = 7;
 // (1680 - 1920 waves for the chip's 2048 wave slots); a single frame runs 56 - 64 waves.  Measured at 30 frames
 // (profiles/r05_attn_key_splits.txt): splits of 32 tiles (29 at the finest level) 691 / 156 / 139 us per level, of 128 tiles
 // 585 / 496 / 254 us: the finest level wants few long splits (partials: 13 KB written and re-read per split), the coarse ones
-// want their 7 - 8.  DVIS_ATTN_KEY_SPLITS (development): another split count.
-KeySplitPlan plan_keysplit(int /*BH*/, int Lq, int Lk) {
+// want their 7 - 8.
+KeySplitPlan plan_keysplit(int Lq, int Lk) {
   KeySplitPlan p;
   p.qchunks = ((Lq + 15) / 16 + kQT - 1) / kQT;
   const int tiles = (Lk + 15) / 16;
-  static const int want = []() { const char *e = getenv("DVIS_ATTN_KEY_SPLITS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
-  int ns = tiles / 8 < want ? tiles / 8 : want;
+  int ns = tiles / 8 < 8 ? tiles / 8 : 8;
   if (ns < 1) ns = 1;
   const int kps = (tiles + ns - 1) / ns * 16;
   p.nsplit = (Lk + kps - 1) / kps;
@@ -824,16 +794,16 @@ __global__ __launch_bounds__(256) void attn_x3_pack_kernel(const float *__restri
   *reinterpret_cast<ah8 *>(dst + 64) = x3_cat(l0, l1);
 }
 
-// Pass 2.  QT query tiles of 16 per wave (a workgroup covers 128 QT queries): every K / V fragment read from LDS serves QT matrix
-// instructions, and a staged K / V tile QT times the queries.
+// Pass 2.  QT = 1 query tile of 16 per wave (a workgroup covers 128 queries).  (QT = 2 measured 6 % slower — 168 registers, one
+// workgroup per CU: profiles/r05_attn_x3_pmc.txt.)
 // IMG: the output as the ROW IMAGE of the GEMM that consumes it (csrc/gemm_x3_tile.hip: [row tile of 128][k-tile of 16][hi, lo][chunk]
 // [128 rows][8 halves], rows = (batch entry, token), k = (head, dim)) x img_scale: a lane holds four dims of a query, two neighbouring
 // lanes one 16-byte fragment (k order 2 of x3_tile_k) — no fp32 attention output, no split in the projection.
-template <int QT, bool IMG = false>
+template <bool IMG>
 __global__ __launch_bounds__(512) void attn_x3_kernel(const _Float16 *__restrict__ ws, float *__restrict__ out, dvis_strides os, int BH,
                                                       int heads, int Lq, int Lk, int *__restrict__ guard_flag, int guard_tag,
                                                       char *__restrict__ img = nullptr, float img_scale = 1.f) {
-  constexpr int KT = kX3KT, NT = KT / 16, RS = kX3Row, RV = kX3RowV;
+  constexpr int QT = 1, KT = kX3KT, NT = KT / 16, RS = kX3Row, RV = kX3RowV;
   __shared__ __attribute__((aligned(16))) _Float16 k_lds[KT * RS], v_lds[KT * RV];      // [key][hi 64 | lo 64 | pad]; V is read transposed
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int j = lane & 15, g = lane >> 4;
@@ -1076,9 +1046,9 @@ DVIS_EXPORT int64_t dvis_attention_ws_bytes_k(int BH, int Lq, int Lk, int d, int
 
 DVIS_EXPORT int64_t dvis_attention_ws_bytes(int BH, int Lq, int Lk, int d) {
   if (BH <= 0 || Lq <= 0 || Lk <= 0 || d <= 0) return 0;
-  const SplitPlan p = plan_split(BH, Lq, Lk);
+  const SplitPlan p = plan_split(Lq, Lk);
   int ns = p.nsplit;
-  if (keysplit_applies(Lq, Lk, d, false, 0, 0)) ns = std::max(ns, plan_keysplit(BH, Lq, Lk).nsplit);   // whichever runs
+  if (keysplit_applies(Lq, Lk, d, false, 0, 0)) ns = std::max(ns, plan_keysplit(Lq, Lk).nsplit);   // whichever runs
   if (ns == 1) return 0;
   return (int64_t)BH * ns * Lq * (d + 2) * (int64_t)sizeof(float);
 }
@@ -1094,11 +1064,6 @@ struct AttnPlan {
   int served_by, nsplit, keys_per_split, qchunks;
 };
 
-static int attn_x3_qt() {
-  static const int qt = []() { const char *e = getenv("DVIS_ATTN_X3_QT"); return e ? atoi(e) : 1; }();     // (development)
-  return qt == 2 ? 2 : 1;
-}
-
 static int attention_decide(int BH, int Lq, int Lk, int d, bool has_mask, int64_t k_row, int64_t v_row, int kernel, AttnPlan *plan) {
   DVIS_REQUIRE(BH > 0 && Lq > 0 && Lk > 0, "attention: bad sizes");
   DVIS_REQUIRE(d == 32 || d == 64, "attention: head dim must be 32 or 64 (got %d)", d);
@@ -1106,23 +1071,21 @@ static int attention_decide(int BH, int Lq, int Lk, int d, bool has_mask, int64_
   DVIS_REQUIRE(kernel == 0 || kernel == 2 || (kernel == 1 && Lk <= 128), "attention: kernel 1 (short keys) needs Lk <= 128 (Lk=%d)", Lk);
   if (kernel == 2) {      // split-f16 long self-attention (ViT blocks): d = 64, no mask, enough query chunks that keys need no split
     DVIS_REQUIRE(d == 64 && !has_mask && Lk >= 128, "attention: kernel 2 (split-f16) serves d = 64 without a mask, Lk >= 128");
-    const int qb = 128 * attn_x3_qt();
-    *plan = AttnPlan{DVIS_ATTN_X3, 1, Lk, (Lq + qb - 1) / qb};
+    *plan = AttnPlan{DVIS_ATTN_X3, 1, Lk, (Lq + 127) / 128};
     return DVIS_OK;
   }
   if (kernel == 0 && keysplit_applies(Lq, Lk, d, has_mask, k_row, v_row)) {
-    const KeySplitPlan kp = plan_keysplit(BH, Lq, Lk);
+    const KeySplitPlan kp = plan_keysplit(Lq, Lk);
     *plan = AttnPlan{DVIS_ATTN_KEYSPLIT, kp.nsplit, kp.keys_per_split, kp.qchunks};
     return DVIS_OK;
   }
-  const SplitPlan p = plan_split(BH, Lq, Lk);
+  const SplitPlan p = plan_split(Lq, Lk);
   // Lk <= 128 (decoder / tracker / refiner self- and cross-attention over queries or frames): one workgroup per (batch, head,
   // 16-query tile) with the keys split over 4 waves (8.0 vs 14.8 us for the tracker's batch-1 call) — for EVERY batch size: the
   // kernels differ in their summation order, and choosing between them by the number of (batch, head) pairs (rounds 1 - 4: <= 384
   // workgroups; at B = 30 the other kernel is 6 us faster per call) made a frame's bits depend on its batch mates.
-  // DVIS_ATTN_SHORT_MAX (development): the old rule.
-  static const long long short_max = []() { const char *e = getenv("DVIS_ATTN_SHORT_MAX"); return e ? atoll(e) : -1ll; }();
-  if (kernel == 1 || (Lk <= 128 && p.nsplit == 1 && (short_max < 0 || (long long)BH * ((Lq + 15) / 16) <= short_max))) {
+  // (plan_split never splits Lk <= 128, so the query-partitioned kernel below only sees longer key sequences.)
+  if (kernel == 1 || Lk <= 128) {
     *plan = AttnPlan{DVIS_ATTN_SHORT, 1, Lk, (Lq + 15) / 16};
     return DVIS_OK;
   }
@@ -1163,12 +1126,8 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
     hipLaunchKernelGGL(attn_x3_pack_kernel, dim3((std::max(Lq, Lk) + 31) / 32, BH, 3), dim3(256), 0, st, q, qs, k, ks, v, vs, wsh, heads, Lq,
                        Lk, scale * kLog2e * 16.f);
     if (const int rc = dvis_check_launch("attn_x3_pack_kernel")) return rc;
-    if (attn_x3_qt() == 2)
-      hipLaunchKernelGGL(attn_x3_kernel<2>, dim3(((BH + 7) / 8) * 8 * plan.qchunks), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
-                         gd.flag, gd.tag);
-    else
-      hipLaunchKernelGGL(attn_x3_kernel<1>, dim3(((BH + 7) / 8) * 8 * plan.qchunks), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
-                         gd.flag, gd.tag);
+    hipLaunchKernelGGL(attn_x3_kernel<false>, dim3(((BH + 7) / 8) * 8 * plan.qchunks), dim3(512), 0, st, wsh, out, os, BH, heads, Lq, Lk,
+                       gd.flag, gd.tag);
     return dvis_check_launch("attn_x3_kernel");
   }
   if (plan.served_by == DVIS_ATTN_KEYSPLIT) {
@@ -1208,15 +1167,12 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
   float *ws_o = (float *)ws;
   float *ws_ml = ws_o ? ws_o + (size_t)BH * p.nsplit * Lq * d : nullptr;
   const dim3 grid(p.nsplit, BH, p.qchunks), block(512);
-  #define DVIS_ATTN(DH_, SHORT_)                                                                                    \
-  hipLaunchKernelGGL((attn_fwd_kernel<DH_, SHORT_>), grid, block, 0, st, q, qs, k, ks, v, vs, out, os, mask, allowed_count, \
-                     heads, Lq, Lk, scale, p.nsplit, p.keys_per_split, ws_o, ws_ml)
-  const bool shrt = Lk <= 128 && p.nsplit == 1;
-  if (d == 32 && shrt) DVIS_ATTN(32, true);
-  else if (d == 32) DVIS_ATTN(32, false);
-  else if (shrt) DVIS_ATTN(64, true);
-  else DVIS_ATTN(64, false);
-#undef DVIS_ATTN
+  if (d == 32)
+    hipLaunchKernelGGL((attn_fwd_kernel<32>), grid, block, 0, st, q, qs, k, ks, v, vs, out, os, mask, allowed_count, heads, Lq, Lk,
+                       scale, p.nsplit, p.keys_per_split, ws_o, ws_ml);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<64>), grid, block, 0, st, q, qs, k, ks, v, vs, out, os, mask, allowed_count, heads, Lq, Lk,
+                       scale, p.nsplit, p.keys_per_split, ws_o, ws_ml);
   int rc = dvis_check_launch("attn_fwd_kernel");
   if (rc != DVIS_OK || p.nsplit == 1) return rc;
   const size_t total = (size_t)BH * Lq * d;
@@ -1242,7 +1198,7 @@ DVIS_EXPORT int dvis_attention_x3_packed(const void *ws, float *out, const int64
   const int BH = B * heads;
   const dvis_strides os{o_strides[0], o_strides[1], o_strides[2]};
   const X3Guard gd = dvis_x3_guard();
-  hipLaunchKernelGGL(attn_x3_kernel<1>, dim3(((BH + 7) / 8) * 8 * ((L + 127) / 128)), dim3(512), 0, (hipStream_t)stream, (const _Float16 *)ws, out,
+  hipLaunchKernelGGL(attn_x3_kernel<false>, dim3(((BH + 7) / 8) * 8 * ((L + 127) / 128)), dim3(512), 0, (hipStream_t)stream, (const _Float16 *)ws, out,
                      os, BH, heads, L, L, gd.flag, gd.tag);
   return dvis_check_launch("attn_x3_kernel");
 }
@@ -1268,7 +1224,7 @@ DVIS_EXPORT int dvis_attention_x3_packed_image(const void *ws, void *image, int 
   const size_t M = (size_t)B * L;
   const X3Guard gd = dvis_x3_guard();
   if (M & 127) hipLaunchKernelGGL(rows_image_tail_kernel, dim3(heads * 4), dim3(256), 0, (hipStream_t)stream, (char *)image, M, heads * 4);
-  hipLaunchKernelGGL((attn_x3_kernel<1, true>), dim3(((BH + 7) / 8) * 8 * ((L + 127) / 128)), dim3(512), 0, (hipStream_t)stream, (const _Float16 *)ws,
+  hipLaunchKernelGGL(attn_x3_kernel<true>, dim3(((BH + 7) / 8) * 8 * ((L + 127) / 128)), dim3(512), 0, (hipStream_t)stream, (const _Float16 *)ws,
                      (float *)nullptr, dvis_strides{0, 0, 0}, BH, heads, L, L, gd.flag, gd.tag, (char *)image, ldexpf(1.f, xexp));
   return dvis_check_launch("attn_x3_kernel (row image)");
 }

@@ -32,7 +32,7 @@ struct CxArgs {
   int stride, W_in, OW, H_in;
   int taps;                                // 1: 1x1; 9: 3x3 with padding 1 (k = tap * C + channel, tap = 3 dy + dx)
   long long HW, HW_in, pixels;             // output pixels per image, input pixels per image, output pixels in total
-  long long tiles;                         // ceil(pixels / (32 NW))
+  long long tiles;                         // ceil(pixels / 256)
   float xscale, inv;
   int *flag;                               // range guard (x3_common.h)
   int tag;
@@ -107,14 +107,15 @@ __device__ __forceinline__ unsigned cx_geom2(const CxArgs &a, long long p) {
   return (unsigned)(n * a.C2 * a.HW2_in * 4) + (unsigned)((oy * a.stride2 * a.W2_in + ox * a.stride2) * 4);
 }
 
-// NW waves x 32 pixels per tile; 8 waves = two per SIMD (<= 256 registers each) cover each other's stalls.
-// IK k-steps per ring item: 2 (three stages) or 4 (= one activation chunk; two stages of up to 64 KB: half the barriers).
+// NW = 8 waves x 32 pixels per tile: two waves per SIMD (<= 256 registers each) cover each other's stalls.
+// IK k-steps per ring item: 2 (three stages; K = 64 / 128) or 4 (= one activation chunk; two stages of up to 64 KB: half the
+// barriers; 2 measured 2 - 5 % slower at K % 256 == 0).
 // IMGIN / IMGOUT: the input / output as operand images (CxArgs::ximg / img) — the 64 .. 512-channel maps INSIDE a bottleneck and the
 // FPN output convolution's input travel that way: the producer's epilogue splits once, the nine taps of a 3x3 consumer re-read the
 // image (8 loads of 16 bytes per chunk and lane instead of 32 of 4 bytes, no split arithmetic in the loop).
-template <int NB, int NW, int IK, bool IMGIN = false, bool IMGOUT = false>
-__global__ __launch_bounds__(NW * 64) void conv1x1_x3_kernel(const CxArgs a) {
-  constexpr int kTile = NW * 32, PW = 2 * IK * NB / NW, STAGES = IK == 4 ? 2 : 3, IPC = 4 / IK;
+template <int NB, int IK, bool IMGIN = false, bool IMGOUT = false>
+__global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
+  constexpr int NW = 8, kTile = NW * 32, PW = 2 * IK * NB / NW, STAGES = IK == 4 ? 2 : 3, IPC = 4 / IK;
   static_assert(2 * IK * NB % NW == 0, "the item's pieces must divide among the waves");
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, g = lane >> 5;
@@ -526,17 +527,16 @@ static int cx_launch(const float *x, const void *packed, const float *bias, cons
   a.ximg = ximg, a.XG_in = (W + 31) / 32;
   const int grid = dvis_x3_persistent_cus();
   hipStream_t st = (hipStream_t)stream;
-  static const int nw = getenv("DVIS_X3_CONV_WAVES") ? atoi(getenv("DVIS_X3_CONV_WAVES")) : 8;
   a.npass = K <= 128 ? 1 : K / 256;
-#define DVIS_CX_LAUNCH(NBV, NWV, IKV)                                                                              \
-  {                                                                                                                \
-    static DvisLdsOptIn opted;                                                                                     \
-    typedef Ring<2 * IKV * NBV / NWV, 32, NWV, (IKV == 4 ? 2 : 3)> R;                                              \
-    a.tiles = (a.pixels + 32 * NWV - 1) / (32 * NWV);                                                              \
-    const size_t lds = (IKV == 4 ? 2 : 3) * R::kItemBytes;                                                         \
-    const int rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<NBV, NWV, IKV>, lds, &opted, "dvis_conv1x1_x3"); \
-    if (rc != DVIS_OK) return rc;                                                                                  \
-    hipLaunchKernelGGL((conv1x1_x3_kernel<NBV, NWV, IKV>), dim3(grid), dim3(NWV * 64), lds, st, a);                \
+#define DVIS_CX_LAUNCH(NBV, IKV)                                                                              \
+  {                                                                                                           \
+    static DvisLdsOptIn opted;                                                                                \
+    typedef Ring<2 * IKV * NBV / 8, 32, 8, (IKV == 4 ? 2 : 3)> R;                                             \
+    a.tiles = (a.pixels + 255) / 256;                                                                         \
+    const size_t lds = (IKV == 4 ? 2 : 3) * R::kItemBytes;                                                    \
+    const int rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<NBV, IKV>, lds, &opted, "dvis_conv1x1_x3"); \
+    if (rc != DVIS_OK) return rc;                                                                             \
+    hipLaunchKernelGGL((conv1x1_x3_kernel<NBV, IKV>), dim3(grid), dim3(512), lds, st, a);                     \
   }
 #define DVIS_CX_LAUNCH_IMG(NBV, IKV, INV, OUTV)                                                                                    \
   {                                                                                                                                \
@@ -544,9 +544,9 @@ static int cx_launch(const float *x, const void *packed, const float *bias, cons
     typedef Ring<2 * IKV * NBV / 8, 8, 8, (IKV == 4 ? 2 : 3)> R;                                                                   \
     a.tiles = (a.pixels + 255) / 256;                                                                                              \
     const size_t lds = (IKV == 4 ? 2 : 3) * R::kItemBytes;                                                                         \
-    const int rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<NBV, 8, IKV, INV, OUTV>, lds, &opted, "dvis_conv_x3_image");    \
+    const int rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<NBV, IKV, INV, OUTV>, lds, &opted, "dvis_conv_x3_image");    \
     if (rc != DVIS_OK) return rc;                                                                                                  \
-    hipLaunchKernelGGL((conv1x1_x3_kernel<NBV, 8, IKV, INV, OUTV>), dim3(grid), dim3(512), lds, st, a);                            \
+    hipLaunchKernelGGL((conv1x1_x3_kernel<NBV, IKV, INV, OUTV>), dim3(grid), dim3(512), lds, st, a);                            \
     return dvis_check_launch("dvis_conv_x3_image");                                                                                \
   }
   if (ximg != nullptr || (image != nullptr && K != 64)) {      // operand images on either side (K = 64 out: the runtime branch of the plain kernels)
@@ -561,16 +561,9 @@ static int cx_launch(const float *x, const void *packed, const float *bias, cons
     DVIS_CX_LAUNCH_IMG(8, 4, false, true)
   }
 #undef DVIS_CX_LAUNCH_IMG
-  static const int ik = getenv("DVIS_X3_CONV_ITEM") ? atoi(getenv("DVIS_X3_CONV_ITEM")) : 4;   // (2: three stages of 32 KB, 2 - 5 % slower)
-  if (K == 64) {
-    if (nw == 8) DVIS_CX_LAUNCH(2, 8, 2) else DVIS_CX_LAUNCH(2, 4, 2)
-  } else if (K == 128) {
-    if (nw == 8) DVIS_CX_LAUNCH(4, 8, 2) else DVIS_CX_LAUNCH(4, 4, 2)
-  } else if (ik == 4) {
-    DVIS_CX_LAUNCH(8, 8, 4)
-  } else {
-    if (nw == 8) DVIS_CX_LAUNCH(8, 8, 2) else DVIS_CX_LAUNCH(8, 4, 2)
-  }
+  if (K == 64) DVIS_CX_LAUNCH(2, 2)
+  else if (K == 128) DVIS_CX_LAUNCH(4, 2)
+  else DVIS_CX_LAUNCH(8, 4)
 #undef DVIS_CX_LAUNCH
   return dvis_check_launch("dvis_conv1x1_x3");
 }

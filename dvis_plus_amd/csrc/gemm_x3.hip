@@ -212,26 +212,24 @@ __device__ __forceinline__ void epilogue(f16v *acc, const EpiArgs &e, const floa
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// out (M x 32 NB npass) = epilogue( x (M x K) W^T ): one projection, its output features in `npass` passes of 32 NB over the
-// same activation fragments.  Weight stream: [pass][K / 32 items of 2 k-steps x NB blocks].
-template <int K, int NB, bool LN>
+// out (M x 32 NB npass) = act( x (M x K) W^T * inv + bias ) at K = 256: one projection, its output features in `npass` passes of
+// 32 NB over the same activation fragments.  Weight stream: [pass][K / 32 items of 2 k-steps x NB blocks].
+template <int NB>
 __global__ __launch_bounds__(kThreads) void x3_linear_kernel(const float *__restrict__ x, int64_t ldx, int64_t M,
                                                              const void *__restrict__ wp, float xscale, int npass,
                                                              const float *__restrict__ xadd, int64_t xadd_rows, EpiArgs e) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  constexpr int KS = K / 16, NI = K / 32;
+  constexpr int K = 256, KS = K / 16, NI = K / 32;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, g = lane >> 5;
   const int64_t ntiles = (M + kTileTok - 1) / kTileTok;
   const int64_t my = blockIdx.x < ntiles ? (ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
   Ring<NB> ring;
   ring.start(wp, lds, NI * npass, (int)(my * NI * npass), wave, lane);
   char *scr = lds + kStages * Ring<NB>::kItemBytes + wave * kScratch;
-  // bias (all passes) | gamma | beta in LDS
+  // bias (all passes) in LDS
   float *cst = (float *)(lds + kStages * Ring<NB>::kItemBytes + kWaves * kScratch);
   const int ntot = 32 * NB * npass;
   for (int i = threadIdx.x; i < ntot; i += kThreads) cst[i] = e.bias ? e.bias[i] : 0.f;
-  if constexpr (LN)
-    for (int i = threadIdx.x; i < 32 * NB; i += kThreads) cst[ntot + i] = e.gamma[i], cst[ntot + 32 * NB + i] = e.beta[i];
   __syncthreads();
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int64_t tok0 = tile * kTileTok + wave * 32;
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(kThreads) void x3_linear_kernel(const float *__rest
         ring.begin_periodic();
         mma_item<2, NB, NB>(stage, lane, acc, xh + 2 * c, xl + 2 * c, [&](int i) { ring.piece(i); });
       }
-      if (tok0 < M) epilogue<NB, LN>(acc, e, cst + pass * 32 * NB, cst + ntot, cst + ntot + 32 * NB, scr, lane, tok0, M, pass * 32 * NB);
+      if (tok0 < M) epilogue<NB, false>(acc, e, cst + pass * 32 * NB, cst + ntot, cst + ntot + 32 * NB, scr, lane, tok0, M, pass * 32 * NB);
     }
   }
 }
@@ -666,7 +664,7 @@ static int x3_linear_impl(const float *x, int64_t ldx, int64_t M, int K, const v
 #define DVIS_X3_RESIDENT(NBV)                                                                                        \
   {                                                                                                                  \
     static DvisLdsOptIn opted;                                                                                       \
-    return x3_launch(x3_linear_kernel<256, NBV, false>, &opted, kStages * Ring<NBV>::kItemBytes + kWaves * kScratch + (size_t)N * 4, \
+    return x3_launch(x3_linear_kernel<NBV>, &opted, kStages * Ring<NBV>::kItemBytes + kWaves * kScratch + (size_t)N * 4, \
                      M, st, "dvis_x3_linear", x, ldx, M, wp, xs, npass, xadd, xadd_rows, e);                         \
   }
   if (relu == 2 || radd) {      // GELU / residual epilogue: the ViT blocks' shapes (N a multiple of 256)

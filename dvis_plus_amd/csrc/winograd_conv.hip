@@ -52,7 +52,6 @@ struct WinoArgs {
   long long tiles;
 };
 
-template <int ABL>   // ABL != 0 (-DDVIS_WINO_ABLATION builds, tools/exp/wino_abl.sh): 1 no patch loads, 2 no transform, 4 no U loads, 8 no MFMAs
 __global__ __launch_bounds__(512, 2) void winograd_f2x3_kernel(const WinoArgs a) {
   extern __shared__ float lds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -111,13 +110,11 @@ __global__ __launch_bounds__(512, 2) void winograd_f2x3_kernel(const WinoArgs a)
   const unsigned u_blk = (unsigned)((kb * 4 + kb16) * nch);
 
   auto load_d = [&](int ch, dvis_f4 (&d)[4]) {
-    if constexpr (ABL & 1) return;
     const unsigned so = (unsigned)(ch * kCc + wv) * plane_bytes;
 #pragma unroll
     for (int i = 0; i < 4; ++i) d[i] = __builtin_bit_cast(dvis_f4, __builtin_amdgcn_raw_buffer_load_b128(rx, rowq[i], so, 0));
   };
   auto load_u = [&](int ch, dvis_f4 (&u)[4]) {
-    if constexpr (ABL & 4) return;
     const unsigned so = ((u_blk + (unsigned)ch) * 2u + (unsigned)half) * 4096u;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -138,7 +135,6 @@ __global__ __launch_bounds__(512, 2) void winograd_f2x3_kernel(const WinoArgs a)
   };
   // V = B^T d B with B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1], position xi = 4 i + jj, to row (xi, channel wv)
   auto transform_store = [&](const dvis_f4 (&q)[4], float *stage) {
-    if constexpr (ABL & 2) return;
     float *vw = stage + wv * kRow + lane;   // 64 lanes, 64 consecutive dwords: conflict-free under the (a/4) % 32 write banking
     float d[16], t[16];
 #pragma unroll
@@ -215,11 +211,8 @@ __global__ __launch_bounds__(512, 2) void winograd_f2x3_kernel(const WinoArgs a)
       vw[(4 * i + 2) * kPos] = t[4 * i + 2] - t[4 * i + 1];
       vw[(4 * i + 3) * kPos] = t[4 * i + 1] - t[4 * i + 3];
     };
-    auto L = [&](int i) {
-      if constexpr (!(ABL & 1)) d[i] = __builtin_bit_cast(dvis_f4, __builtin_amdgcn_raw_buffer_load_b128(rx, rowq[i], so_load, 0));
-    };
+    auto L = [&](int i) { d[i] = __builtin_bit_cast(dvis_f4, __builtin_amdgcn_raw_buffer_load_b128(rx, rowq[i], so_load, 0)); };
     auto item = [&](int m) {   // m = 0..31, after MFMA pair m
-      if constexpr (ABL & 2) return;
       if (m < 4) S(m, 0);
       else if (m < 6) T(m - 4);
       else if (m < 10) S(m - 6, 1);
@@ -235,12 +228,10 @@ __global__ __launch_bounds__(512, 2) void winograd_f2x3_kernel(const WinoArgs a)
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
           const int m = (x8 * 2 + s) * 2 + h2;
-          if constexpr (!(ABL & 8)) {
-            const float av = u[x8 >> 1][(x8 & 1) * 2 + s];
+          const float av = u[x8 >> 1][(x8 & 1) * 2 + s];
 #pragma unroll
-            for (int tb = 2 * h2; tb < 2 * h2 + 2; ++tb)
-              acc[x8][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[x8 & 1][s][tb], acc[x8][tb], 0, 0, 0);
-          }
+          for (int tb = 2 * h2; tb < 2 * h2 + 2; ++tb)
+            acc[x8][tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[x8 & 1][s][tb], acc[x8][tb], 0, 0, 0);
           if (x8 + 1 < 8 && s == 1) b[(x8 + 1) & 1][h2] = vr[((x8 + 1) * kPos + h2 * 4 * kRow) / 4];   // next position's operands
           item(m);
           fence();
@@ -428,19 +419,6 @@ DVIS_EXPORT int dvis_conv3x3_winograd(const float *x, const float *uf, const flo
   a.nsp = (int)nsp;
   const size_t lds_bytes = 2 * kStage * sizeof(float);
   const unsigned grid = (unsigned)(((nsp + 7) / 8) * 8 * (K / kKw));
-#ifdef DVIS_WINO_ABLATION   // development builds only (tools/exp/wino_abl.sh): the kernel with parts switched off — WRONG results
-  static const int abl = getenv("DVIS_WINO_ABL") ? atoi(getenv("DVIS_WINO_ABL")) : 0;
-  switch (abl) {
-#define DVIS_WINO_CASE(V)                                                                                          \
-  case V:                                                                                                          \
-    hipLaunchKernelGGL(winograd_f2x3_kernel<V>, dim3(grid), dim3(512), lds_bytes, (hipStream_t)stream, a);          \
-    return dvis_check_launch("dvis_conv3x3_winograd");
-    DVIS_WINO_CASE(1) DVIS_WINO_CASE(2) DVIS_WINO_CASE(3) DVIS_WINO_CASE(4) DVIS_WINO_CASE(7) DVIS_WINO_CASE(8) DVIS_WINO_CASE(11)
-#undef DVIS_WINO_CASE
-  default:
-    break;
-  }
-#endif
-  hipLaunchKernelGGL(winograd_f2x3_kernel<0>, dim3(grid), dim3(512), lds_bytes, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(winograd_f2x3_kernel, dim3(grid), dim3(512), lds_bytes, (hipStream_t)stream, a);
   return dvis_check_launch("dvis_conv3x3_winograd");
 }

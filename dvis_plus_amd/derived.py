@@ -54,7 +54,7 @@ class Table:
     def entry(self, key_obj, kind, sources, make, extra=(), note=None):
         """The refreshed entry: `.value`, and `.note` = `note()` of the call that created the entry (it survives re-makes)."""
         k = (id(key_obj), kind)
-        with self.lock:                # (stream()'s phase-B thread and the main thread both pack: the LRU order is shared state)
+        with self.lock:                # (callers on several host threads may pack: the LRU order is shared state)
             ent = self.d.get(k)
             if ent is None:
                 ent = self.d[k] = Derived()

@@ -142,9 +142,6 @@ class _VideoBase(nn.Module):
         # advance TOGETHER in one pass (same results per clip; the recurrence's ~65 launch-bound kernels per frame are paid
         # once for the whole round).  Per-clip latency grows by (tracker_batch - 1) segmenter passes.
         self.tracker_batch = max(1, int(os.environ.get("DVIS_TRACKER_BATCH", "1")))
-        # stream(): phase B on its own host thread (DVIS_STREAM_THREAD=1).  Off by default: measured per rank with
-        # tools/rank_emulation.py it buys 0 - 3 % — the serial host is not what keeps the two phases from overlapping
-        self.stream_thread = os.environ.get("DVIS_STREAM_THREAD", "0") == "1"
         self.stream_timing = False            # stream(): make the per-clip "ready_event" a timing event (bench latency)
         # bench.py only: let a clip's input dict carry its own calibrated "object_mask_threshold" (random-init class
         # scores are near-uniform).  Off by default: the reference's input dicts have no such key.
@@ -199,12 +196,10 @@ class _VideoBase(nn.Module):
     def _new_tracker_stream():
         """The stream phase B runs on.  Its kernels are few-workgroup links of a strictly sequential chain; next to phase A's
         device-filling kernels each of them takes 4-6x its stand-alone time (profiles/r03_bench_kernel_stats.csv) — invisible
-        while phase A is 140 ms long, the critical path when it is 20 ms (a rank of an 8-GPU job).  Measured and NOT the
-        answer (profiles/r03_rank_emulation_matrix.txt): a high-priority stream (DVIS_SIDE_PRIORITY=-1:
-        140 -> 162 ms per clip on one GPU) and disjoint compute-unit masks for the two streams (hipExtStreamCreateWithCUMask,
-        16 / 32 / 64 CUs for phase B: 219 - 232 ms)."""
-        pr = int(os.environ.get("DVIS_SIDE_PRIORITY", "0"))
-        return torch.cuda.Stream(priority=pr)
+        while phase A is 140 ms long, the critical path when it is 20 ms (a rank of an 8-GPU job).  Default priority: a
+        high-priority stream (140 -> 162 ms per clip) and disjoint compute-unit masks for the two streams (219 - 232 ms) were
+        measured and lost (profiles/r03_rank_emulation_matrix.txt)."""
+        return torch.cuda.Stream()
 
     @property
     def clip_shard(self):
@@ -234,35 +229,12 @@ class _VideoBase(nn.Module):
             x = torch.nn.functional.pad(x, (0, Wp - W, 0, Hp - H))
         return x, (H, W)
 
-    def _reserve_scope(self, stage):
-        """Inside stream(): the persistent split-f16 grids of `stage` leave `_stream_reserve` CUs to the side stream when the
-        reserve is scoped to that stage (DVIS_X3_RESERVE_SCOPE=backbone; development).  Default "phase_a": the whole of phase A
-        leaves the CUs free.  Measured in round 6 (profiles/r06_reserve_scope.txt): phase B of the previous round starts on the
-        device when this round's phase A does, so scoping the reserve to the 22 ms backbone looked free — it is not: 380 against
-        388 frames/s (phase B's host-paced chain outlasts the backbone, and its few-workgroup kernels then queue behind
-        full-device grids)."""
-        import contextlib
-        r = getattr(self, "_stream_reserve_now", 0)
-        if not r or self._reserve_scope_name != stage:
-            return contextlib.nullcontext()
-
-        @contextlib.contextmanager
-        def scope():
-            prev = native.lib().dvis_x3_set_reserve(r)
-            try:
-                yield
-            finally:
-                native.lib().dvis_x3_set_reserve(prev)
-        return scope()
-
-    _reserve_scope_name = os.environ.get("DVIS_X3_RESERVE_SCOPE", "phase_a")
-
     def encode(self, images):
         """Backbone + pixel decoder over this rank's frames: (multi_scale_features, mask_features (t,Cm,h,w))."""
         chunk = segmenter_frames_per_call(len(images), images.shape[-2], images.shape[-1], self.segmenter_chunk)
         ms, mf = [], []
         for s in range(0, len(images), chunk):
-            with Fn.x3_stage("backbone"), self._reserve_scope("backbone"):
+            with Fn.x3_stage("backbone"):
                 feats = self.backbone(images[s:s + chunk])
             f, _, m = self.sem_seg_head.pixel_decoder.forward_features(feats)
             mf.append(f)
@@ -906,7 +878,7 @@ class DVIS_Plus_offline(_VideoBase):
             return outs
 
         def hand_over(outs):
-            """(consumer's thread) The outputs were produced (and allocated) on the side stream; the caller consumes them on
+            """The outputs were produced (and allocated) on the side stream; the caller consumes them on
             ITS stream: order it behind phase B of the round and tell the allocator about the second stream."""
             if overlap:
                 main.wait_event(outs[0]["ready_event"])
@@ -924,17 +896,11 @@ class DVIS_Plus_offline(_VideoBase):
         yield from self._stream_rounds(videos, per_round, sharded_owner, overlap, main, side, phase_b, hand_over)
 
     def _segment_round_reserved(self, chunk, shift, rotate):
-        """_segment_round with the persistent split-f16 grids leaving `_stream_reserve` CUs to the side stream — for the stage
-        `_reserve_scope` names, or for all of phase A."""
+        """_segment_round with the persistent split-f16 grids leaving `_stream_reserve` CUs to the side stream for all of phase A.
+        (Scoping the reserve to the backbone alone lost: 380 against 388 frames/s, profiles/r06_reserve_scope.txt.)"""
         r = getattr(self, "_stream_reserve", 0)
         if not r:
             return self._segment_round(chunk, shift=shift, rotate=rotate)
-        if self._reserve_scope_name != "phase_a":
-            self._stream_reserve_now = r
-            try:
-                return self._segment_round(chunk, shift=shift, rotate=rotate)
-            finally:
-                self._stream_reserve_now = 0
         prev = native.lib().dvis_x3_set_reserve(r)
         try:
             return self._segment_round(chunk, shift=shift, rotate=rotate)
@@ -943,10 +909,6 @@ class DVIS_Plus_offline(_VideoBase):
 
     def _stream_rounds(self, videos, per_round, sharded_owner, overlap, main, side, phase_b, hand_over):
         import itertools
-        if overlap and self.stream_thread:
-            yield from self._stream_threaded(videos, per_round, sharded_owner, main, phase_b, hand_over)
-            return
-
         it, prev, n = iter(videos), None, 0
         while True:
             chunk = list(itertools.islice(it, per_round))
@@ -973,83 +935,6 @@ class DVIS_Plus_offline(_VideoBase):
                 break
         if overlap:
             main.wait_stream(side)
-
-    def _stream_threaded(self, videos, per_round, sharded_owner, main, phase_b, hand_over):
-        """stream() with phase B on its own HOST thread (opt-in: `stream_thread`).  Phase B blocks the host for as long as
-        the tracker's chain of small kernels and host-side assignments runs (~24 ms per 30-frame clip); with one host thread
-        the next round's phase A can only be enqueued after that.  Here this thread only enqueues phase A (bounded: two rounds
-        ahead) and hands finished rounds to the consumer; the worker runs phase B round by round in order — every collective
-        of the pipeline is issued by it, in the same order on every rank.  The waits of phase B (event / stream
-        synchronisation, the C assignment chain through ctypes) release the GIL.  Results are those of the single-threaded
-        schedule: same kernels, same order per stream.  Measured (tools/rank_emulation.py, one rank of 8: 38.5 -> 37.4 ms per
-        clip; owner rounds 19.2 -> 19.2): the host was not the limiter — phase B's kernels run 4-6x slower NEXT to phase A's
-        than alone, whoever enqueues them — so this stays off."""
-        import itertools
-        import queue
-        import threading
-        q_in, q_out = queue.Queue(maxsize=2), queue.Queue()
-        device = self.device
-
-        def worker():
-            torch.cuda.set_device(device)
-            with torch.no_grad():
-                while True:
-                    sts = q_in.get()
-                    if sts is None:
-                        return
-                    try:
-                        q_out.put(("ok", phase_b(sts)))
-                    except BaseException as e:      # noqa: BLE001 — re-raised in the consumer's thread
-                        q_out.put(("err", e))
-                        return
-        th = threading.Thread(target=worker, name="dvis-phase-b", daemon=True)
-        th.start()
-        pending = 0
-
-        def take(block):
-            nonlocal pending
-            kind, val = q_out.get(block=block)
-            pending -= 1
-            if kind == "err":
-                pending = 0
-                raise val
-            return hand_over(val)
-        try:
-            it, n = iter(videos), 0
-            while True:
-                chunk = list(itertools.islice(it, per_round))
-                if not chunk:
-                    break
-                with Fn.no_autocast():
-                    sts = self._segment_round_reserved(chunk, n if sharded_owner else 0, sharded_owner)
-                n += len(chunk)
-                done = torch.cuda.Event()
-                done.record(main)
-                for st in sts:
-                    st["done"] = done
-                while True:                         # hand the round to the worker; meanwhile pass finished rounds on
-                    try:
-                        q_in.put(sts, timeout=0.002)
-                        pending += 1
-                        break
-                    except queue.Full:
-                        if not th.is_alive() and q_out.empty():
-                            raise RuntimeError("stream(): the phase-B thread died")
-                    while not q_out.empty():
-                        yield from take(False)
-                while not q_out.empty():
-                    yield from take(False)
-            while pending:
-                yield from take(True)
-        finally:
-            try:
-                while True:                         # (consumer stopped early / error: drop what is queued)
-                    q_in.get_nowait()
-            except queue.Empty:
-                pass
-            q_in.put(None)
-            th.join()
-            main.wait_stream(self._tracker_stream)
 
     def forward(self, batched_inputs):
         """.eval(): the reference's output dict of one video.  .train(): the weighted loss dict of the refiner stage."""

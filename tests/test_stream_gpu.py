@@ -109,8 +109,6 @@ def test_phase_b_is_bit_reproducible():
         outs = list(m.stream([video, _clip(7, 4), _clip(7, 5)]))
         torch.cuda.synchronize()
         assert torch.equal(outs[0]["pred_masks"], ref[0]) and outs[0]["segments_infos"] == ref[1]
-        # ... and with phase B on its own host thread (opt-in schedule): the same bits, clips in order, errors re-raised
-        m.stream_thread = True
         # (only clip 0 has replayed phase-A tensors: at this small size the library kernels of phase A are not reproducible
         # from call to call, so the other clips are checked for ORDER — their lengths differ — not for bits)
         clips = [video, _clip(6, 4), _clip(5, 5), _clip(4, 6), _clip(3, 7)]
