@@ -19,6 +19,7 @@
 #include "x3_common.h"
 
 DVIS_EXPORT int64_t dvis_conv_x3_image_bytes(int64_t N, int C, int H, int W);
+DVIS_EXPORT int dvis_conv_x3_gn_fold_supported(int K, int G, int64_t HW);
 
 namespace {
 
@@ -52,6 +53,14 @@ struct CxArgs {
   // are packed to match (dvis_conv_x3_pack_image).  Nothing is split: a chunk is 8 loads of 16 bytes per lane.
   const void *ximg;
   int XG_in;
+  // FOLD & 1 (fp32 map out, K % 256 == 0, HW % 32 == 0): the GroupNorm(K / 8, K) statistics of the stored values beside the stores —
+  // per (image, group, 32-pixel wave slot) one (sum, sum of squares) in fp64, [n][group][slot][2]; dvis_group_norm_finalize sums them
+  double *gn_part;
+  int slots;                               // HW / 32
+  // FOLD & 2 (1x1 from an fp32 map, C = 256, HW % 32 == 0): the activations are read as relu?(x * in_scale[n * C + c] +
+  // in_shift[n * C + c]) — dvis_scale_shift_act's arithmetic, applied before the split
+  const float *in_scale, *in_shift;
+  int in_relu;
 };
 
 // the w-th work item of workgroup b: XCD x = b % 8 owns the tiles t = x (mod 8); its workgroups deal (tile, pass) pairs
@@ -107,16 +116,31 @@ __device__ __forceinline__ unsigned cx_geom2(const CxArgs &a, long long p) {
   return (unsigned)(n * a.C2 * a.HW2_in * 4) + (unsigned)((oy * a.stride2 * a.W2_in + ox * a.stride2) * 4);
 }
 
+// One step of a reduce-scatter over the wave: of two values, a lane keeps the one that bit B of its number selects and adds what
+// its partner (lane ^ 1 << B) held of it.  Six steps leave each of 64 values summed over the wave in one lane; a fixed order of
+// additions: the same bits on every run.
+template <int B>
+__device__ __forceinline__ double cx_fold(double a0, double a1, int lane) {
+  const bool up = (lane >> B) & 1;
+  return (up ? a1 : a0) + __shfl_xor(up ? a0 : a1, 1 << B);
+}
+
 // NW = 8 waves x 32 pixels per tile: two waves per SIMD (<= 256 registers each) cover each other's stalls.
 // IK k-steps per ring item: 2 (three stages; K = 64 / 128) or 4 (= one activation chunk; two stages of up to 64 KB: half the
 // barriers; 2 measured 2 - 5 % slower at K % 256 == 0).
 // IMGIN / IMGOUT: the input / output as operand images (CxArgs::ximg / img) — the 64 .. 512-channel maps INSIDE a bottleneck and the
 // FPN output convolution's input travel that way: the producer's epilogue splits once, the nine taps of a 3x3 consumer re-read the
 // image (8 loads of 16 bytes per chunk and lane instead of 32 of 4 bytes, no split arithmetic in the loop).
-template <int NB, int IK, bool IMGIN = false, bool IMGOUT = false>
+// FOLD: the GroupNorm around the pixel decoder's mask-path convolutions (CxArgs::gn_part, CxArgs::in_scale): 1 = the statistics of
+// the output from the epilogue's registers, 2 = the previous layer's normalisation (+ ReLU) applied to the activations as they are
+// read.  Both assume that a wave's 32 pixels lie in ONE image (HW % 32 == 0).
+template <int NB, int IK, bool IMGIN = false, bool IMGOUT = false, int FOLD = 0>
 __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
   constexpr int NW = 8, kTile = NW * 32, PW = 2 * IK * NB / NW, STAGES = IK == 4 ? 2 : 3, IPC = 4 / IK;
+  constexpr bool kStats = (FOLD & 1) != 0, kAffine = (FOLD & 2) != 0;
   static_assert(2 * IK * NB % NW == 0, "the item's pieces must divide among the waves");
+  static_assert(FOLD == 0 || (NB == 8 && !IMGOUT), "the folded GroupNorm forms: 256 channels per pass, fp32 map out");
+  static_assert(!kAffine || !IMGIN, "the input affine applies to an fp32 map");
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, g = lane >> 5;
   const int NCC = a.C / 64, NC1 = a.taps * NCC, NC = NC1 + a.C2 / 64, NI = IPC * NC;   // chunks per tap, of source 1, in all; ring items per work item
@@ -186,6 +210,17 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
   long long tile;
   int pass;
   cx_item(a, 0, &tile, &pass);
+  // kAffine (C = 256): the (scale | shift) rows of the wave's image, 1 KB each, in 2 KB of LDS per wave behind the ring, fetched
+  // by LDS-DMA.  A fetch is requested BEFORE activation loads that are waited for before the table is read (requests complete in
+  // order): no wait of its own, and on top of the 32 loads the ring's counted wait leaves out it can only make that wait stricter.
+  char *tab = lds + STAGES * RingT::kItemBytes + wave * (2 * kPiece);
+  auto load_tab = [&](long long t) {
+    long long n = (t * kTile + wave * 32) / a.HW;
+    n = n < a.N ? n : a.N - 1;             // (a wave past the last pixel: any valid row)
+    glds16((const char *)(a.in_scale + n * 256) + lane * 16, tab);
+    glds16((const char *)(a.in_shift + n * 256) + lane * 16, tab + kPiece);
+  };
+  if constexpr (kAffine) load_tab(tile);
   CxGeom gm = cx_geom(a, tile * kTile + wave * 32 + j);
   unsigned gm2 = cx_geom2(a, tile * kTile + wave * 32 + j);
   if constexpr (IMGIN)
@@ -229,10 +264,27 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
         for (int i = 0; i < 32; ++i) asm volatile("" : "+v"(raw[i]));
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          const f4 lo4 = {raw[8 * s], raw[8 * s + 1], raw[8 * s + 2], raw[8 * s + 3]};
-          const f4 hi4 = {raw[8 * s + 4], raw[8 * s + 5], raw[8 * s + 6], raw[8 * s + 7]};
+          f4 lo4 = {raw[8 * s], raw[8 * s + 1], raw[8 * s + 2], raw[8 * s + 3]};
+          f4 hi4 = {raw[8 * s + 4], raw[8 * s + 5], raw[8 * s + 6], raw[8 * s + 7]};
+          if constexpr (kAffine) {         // (taps == 1, one source: the chunk being multiplied is chunk kc)
+            // one k-step's 16 table values at a time, used on the spot: hipcc otherwise fetches all 64 at the loop's head and sinks the
+            // arithmetic into the products with them — 64 registers that are not there beside the accumulators
+            asm volatile("" ::: "memory");
+            const float *ts = (const float *)tab + 64 * kc + 16 * s + 8 * g;
+            const f4 s0 = *(const f4 *)ts, s1 = *(const f4 *)(ts + 4), h0 = *(const f4 *)(ts + 256), h1 = *(const f4 *)(ts + 260);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const float t0 = __builtin_fmaf(lo4[e], s0[e], h0[e]), t1 = __builtin_fmaf(hi4[e], s1[e], h1[e]);
+              lo4[e] = a.in_relu ? fmaxf(t0, 0.f) : t0;
+              hi4[e] = a.in_relu ? fmaxf(t1, 0.f) : t1;
+            }
+            asm volatile("" : "+v"(lo4), "+v"(hi4));
+            __builtin_amdgcn_sched_barrier(0);
+          }
           split8(lo4, hi4, a.xscale, xh[s], xl[s]);
         }
+        if constexpr (kAffine)
+          if (kc + 1 == NC && more) load_tab(ntile);      // the table's last reader is above, the next item's first chunk below
         // ALWAYS 32 loads here (the ring's counted wait relies on it): the next chunk, the next item's first, or nothing (OOB)
         if (++cc == NCC) cc = 0, ++tap;
         const bool first = kc + 1 < NC1, sec = !first && kc + 1 < NC;      // wave-uniform; the second source's chunks follow the first's
@@ -291,9 +343,14 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
         continue;
       }
     }
+    // kStats: GroupNorm group = the 8 channels (nb, q) of the two half-waves.  The (sum, sum of squares) of a group, the 4 groups
+    // of a block and the 8 blocks each go through reduce-scatter steps as soon as a pair is complete: lane L ends with ONE total
+    // over the wave's 32 pixels — statistic L >> 5, q = (L >> 4 & 1) + 2 (L >> 3 & 1), nb = (L >> 2 & 1) + 2 (L >> 1 & 1) + 4 (L & 1).
+    double gw[8], gw2[4], gw4[2], gtot = 0.0;      // (kStats: NB = 8)
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       float rv[16];                    // the shortcut's 16 values of the block as one batch of requests
+      double gq[4];
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         rv[r] = a.res ? __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
@@ -304,6 +361,7 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
         const int co = co0 + 32 * nb + 8 * q + 4 * g;
         f4 b = {0.f, 0.f, 0.f, 0.f};
         if (a.bias) b = *(const f4 *)(a.bias + co);
+        double gsum = 0.0, gsq = 0.0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const unsigned o = obase + (unsigned)(co + i) * ochan;
@@ -311,7 +369,27 @@ __global__ __launch_bounds__(512) void conv1x1_x3_kernel(const CxArgs a) {
           chk = __builtin_fmaf(v, 0.f, chk);
           if (a.relu) v = x3_relu(v);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), ry, o, 0, 0);
+          if constexpr (kStats) {          // the value as stored; a lane past the last pixel adds nothing
+            const double d = p < a.pixels ? (double)v : 0.0;
+            gsum = i == 0 ? d : gsum + d;
+            gsq = i == 0 ? d * d : __builtin_fma(d, d, gsq);
+          }
         }
+        if constexpr (kStats) gq[q] = cx_fold<5>(gsum, gsq, lane);
+      }
+      if constexpr (kStats) {
+        gw[nb] = cx_fold<3>(cx_fold<4>(gq[0], gq[1], lane), cx_fold<4>(gq[2], gq[3], lane), lane);
+        if (nb % 2 == 1) gw2[nb / 2] = cx_fold<2>(gw[nb - 1], gw[nb], lane);
+        if (nb % 4 == 3) gw4[nb / 4] = cx_fold<1>(gw2[nb / 2 - 1], gw2[nb / 2], lane);
+        if (nb == NB - 1) gtot = cx_fold<0>(gw4[0], gw4[1], lane);
+      }
+    }
+    if constexpr (kStats) {
+      const long long pw = tile * kTile + wave * 32;     // the wave's first pixel: its 32 pixels share the image (HW % 32 == 0)
+      if (pw < a.pixels) {
+        const long long nw = pw / a.HW, slot = (pw - nw * a.HW) >> 5;
+        const int group = co0 / 8 + 4 * (((lane >> 2) & 1) + 2 * ((lane >> 1) & 1) + 4 * (lane & 1)) + ((lane >> 4) & 1) + 2 * ((lane >> 3) & 1);
+        a.gn_part[((nw * (a.K / 8) + group) * a.slots + slot) * 2 + (lane >> 5)] = gtot;
       }
     }
     if (a.flag != nullptr && chk != chk && p < a.pixels) atomicCAS(a.flag, 0, a.tag);
@@ -414,9 +492,17 @@ DVIS_EXPORT int dvis_conv1x1_x3_pack(const float *w, int K, int C, int wexp, voi
   return dvis_check_launch("dvis_conv1x1_x3_pack");
 }
 
+// the GroupNorm folded into a launch (CxArgs::gn_part / in_scale): statistics out, or the previous layer's affine (+ ReLU) in
+struct CxFold {
+  double *gn_part;
+  const float *in_scale, *in_shift;
+  int in_relu;
+};
+
 static int cx_launch(const float *x, const void *packed, const float *bias, const float *res, float *y, int N, int C, int K, int H, int W,
                      int stride, int taps, int xexp, int wexp, int relu, void *stream, const float *x2 = nullptr, int C2 = 0, int H2 = 0,
-                     int W2 = 0, int stride2 = 1, void *image = nullptr, int oexp = 0, const void *ximg = nullptr);
+                     int W2 = 0, int stride2 = 1, void *image = nullptr, int oexp = 0, const void *ximg = nullptr,
+                     const CxFold *fold = nullptr);
 
 DVIS_EXPORT int dvis_conv1x1_x3_dual(const float *x, const float *x2, const void *packed, const float *bias, const float *res, float *y,
                                      int N, int C, int C2, int K, int H, int W, int H2, int W2, int stride2, int xexp, int wexp, int relu,
@@ -428,9 +514,23 @@ DVIS_EXPORT int dvis_conv1x1_x3_dual(const float *x, const float *x2, const void
   return cx_launch(x, packed, bias, res, y, N, C, K, H, W, 1, 1, xexp, wexp, relu, stream, x2, C2, H2, W2, stride2);
 }
 
+/* in_scale / in_shift (N * C, both or neither): x is read as in_relu?(x * in_scale[n * C + c] + in_shift[n * C + c]) — the GroupNorm
+ * (+ ReLU) of the layer before, dvis_scale_shift_act's arithmetic without its pass over the map; C = 256, stride 1.
+ * gn_part (N * (K / 8) * (H * W / 32) * 2 doubles): the statistics of GroupNorm(K / 8, K) on y, for dvis_group_norm_finalize.
+ * Either needs K %% 256 == 0 and H * W %% 32 == 0 (dvis_conv_x3_gn_fold_supported); one of the two per launch. */
 DVIS_EXPORT int dvis_conv1x1_x3(const float *x, const void *packed, const float *bias, const float *res, float *y, int N, int C, int K,
-                                int H, int W, int stride, int xexp, int wexp, int relu, void *stream) {
-  return cx_launch(x, packed, bias, res, y, N, C, K, H, W, stride, 1, xexp, wexp, relu, stream);
+                                int H, int W, int stride, int xexp, int wexp, int relu, void *stream, const float *in_scale,
+                                const float *in_shift, int in_relu, double *gn_part) {
+  DVIS_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "dvis_conv1x1_x3: in_scale and in_shift together");
+  const CxFold fold = {gn_part, in_scale, in_shift, in_relu};
+  return cx_launch(x, packed, bias, res, y, N, C, K, H, W, stride, 1, xexp, wexp, relu, stream, nullptr, 0, 0, 0, 1, nullptr, 0, nullptr,
+                   (gn_part || in_scale) ? &fold : nullptr);
+}
+
+/* Do the folded GroupNorm forms of dvis_conv1x1_x3 / dvis_conv_x3_image serve K output channels in G groups on maps of HW pixels?
+ * A wave's 32 pixels in one image, a group = the 8 channels one accumulator row pair holds. */
+DVIS_EXPORT int dvis_conv_x3_gn_fold_supported(int K, int G, int64_t HW) {
+  return K > 0 && K % 256 == 0 && G > 0 && K == 8 * G && HW > 0 && HW % 32 == 0;
 }
 
 /* relu?(conv1x1(x, w) + bias) for K = 64 output channels, written as the operand image csrc/bneck_x3.hip reads (dvis_bneck_x3_image_bytes(N, H, W)
@@ -469,7 +569,7 @@ DVIS_EXPORT int dvis_conv_x3_pack_image(const float *w, int K, int C, int taps, 
  * xexp: the exponent the INPUT was / is split with.  K = 128 or K %% 256 == 0; taps 1 (1x1) or 9 (3x3, padding 1); stride 1 or 2. */
 DVIS_EXPORT int dvis_conv_x3_image(const void *ximg, const float *x, const void *packed, const float *bias, const float *res, float *y,
                                    void *image, int N, int C, int K, int H, int W, int stride, int taps, int xexp, int wexp, int oexp, int relu,
-                                   void *stream) {
+                                   void *stream, double *gn_part) {
   DVIS_REQUIRE(ximg != nullptr || image != nullptr, "dvis_conv_x3_image: neither side is an operand image (use dvis_conv1x1_x3 / dvis_conv3x3_x3)");
   DVIS_REQUIRE((ximg != nullptr) != (x != nullptr), "dvis_conv_x3_image: exactly one of ximg and x");
   DVIS_REQUIRE((image != nullptr) != (y != nullptr), "dvis_conv_x3_image: exactly one of image and y");
@@ -480,7 +580,10 @@ DVIS_EXPORT int dvis_conv_x3_image(const void *ximg, const float *x, const void 
   const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
   DVIS_REQUIRE(dvis_conv_x3_image_bytes(N, C, H, W) < ((int64_t)1 << 31) && dvis_conv_x3_image_bytes(N, K, OH, OW) < ((int64_t)1 << 31),
                "dvis_conv_x3_image: images must stay below 2 GiB");
-  return cx_launch(x, packed, bias, res, y, N, C, K, H, W, stride, taps, xexp, wexp, relu, stream, nullptr, 0, 0, 0, 1, image, oexp, ximg);
+  DVIS_REQUIRE(gn_part == nullptr || (ximg != nullptr && y != nullptr), "dvis_conv_x3_image: statistics with an image in and an fp32 map out");
+  const CxFold fold = {gn_part, nullptr, nullptr, 0};
+  return cx_launch(x, packed, bias, res, y, N, C, K, H, W, stride, taps, xexp, wexp, relu, stream, nullptr, 0, 0, 0, 1, image, oexp, ximg,
+                   gn_part ? &fold : nullptr);
 }
 
 DVIS_EXPORT int64_t dvis_conv3x3_x3_packed_bytes(int C, int K) {
@@ -507,7 +610,7 @@ DVIS_EXPORT int dvis_conv3x3_x3(const float *x, const void *packed, const float 
 
 static int cx_launch(const float *x, const void *packed, const float *bias, const float *res, float *y, int N, int C, int K, int H, int W,
                      int stride, int taps, int xexp, int wexp, int relu, void *stream, const float *x2, int C2, int H2, int W2, int stride2,
-                     void *image, int oexp, const void *ximg) {
+                     void *image, int oexp, const void *ximg, const CxFold *fold) {
   DVIS_REQUIRE((x || ximg) && packed && (y || image), "dvis_conv1x1_x3: null operand");
   DVIS_REQUIRE(stride == 1 || stride == 2, "dvis_conv1x1_x3: stride %d", stride);
   const int OH = (H + stride - 1) / stride, OW = (W + stride - 1) / stride;
@@ -528,6 +631,37 @@ static int cx_launch(const float *x, const void *packed, const float *bias, cons
   const int grid = dvis_x3_persistent_cus();
   hipStream_t st = (hipStream_t)stream;
   a.npass = K <= 128 ? 1 : K / 256;
+  if (fold != nullptr) {       // the folded GroupNorm forms: NB = 8 only, instantiated for what the pixel decoder's mask path launches
+    DVIS_REQUIRE(dvis_conv_x3_gn_fold_supported(K, K / 8, a.HW) && image == nullptr && x2 == nullptr, "dvis_conv1x1_x3: folded GroupNorm "
+                 "needs K %% 256 == 0, H * W %% 32 == 0, an fp32 map out, one source (K %d, %d x %d)", K, OH, OW);
+    DVIS_REQUIRE((fold->gn_part != nullptr) != (fold->in_scale != nullptr), "dvis_conv1x1_x3: statistics or an input affine, not both");
+    a.tiles = (a.pixels + 255) / 256;
+    a.gn_part = fold->gn_part, a.slots = (int)(a.HW / 32);
+    a.in_scale = fold->in_scale, a.in_shift = fold->in_shift, a.in_relu = fold->in_relu;
+    typedef Ring<8, 32, 8, 2> R;
+    size_t lds = 2 * R::kItemBytes;
+    int rc;
+    if (fold->in_scale != nullptr) {
+      DVIS_REQUIRE(ximg == nullptr && taps == 1 && stride == 1 && C == 256 && ((uintptr_t)fold->in_scale | (uintptr_t)fold->in_shift) % 16 == 0,
+                   "dvis_conv1x1_x3: an input affine needs a 1x1 stride-1 launch from an fp32 map of 256 channels (C %d), 16-byte aligned rows", C);
+      static DvisLdsOptIn opted;
+      lds += (size_t)8 * 2 * kPiece;     // (scale | shift) of its image per wave
+      rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<8, 4, false, false, 2>, lds, &opted, "dvis_conv1x1_x3");
+      if (rc != DVIS_OK) return rc;
+      hipLaunchKernelGGL((conv1x1_x3_kernel<8, 4, false, false, 2>), dim3(grid), dim3(512), lds, st, a);
+    } else if (ximg != nullptr) {
+      static DvisLdsOptIn opted;
+      rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<8, 4, true, false, 1>, lds, &opted, "dvis_conv_x3_image");
+      if (rc != DVIS_OK) return rc;
+      hipLaunchKernelGGL((conv1x1_x3_kernel<8, 4, true, false, 1>), dim3(grid), dim3(512), lds, st, a);
+    } else {
+      static DvisLdsOptIn opted;
+      rc = dvis_lds_opt_in((const void *)conv1x1_x3_kernel<8, 4, false, false, 1>, lds, &opted, "dvis_conv1x1_x3");
+      if (rc != DVIS_OK) return rc;
+      hipLaunchKernelGGL((conv1x1_x3_kernel<8, 4, false, false, 1>), dim3(grid), dim3(512), lds, st, a);
+    }
+    return dvis_check_launch(ximg ? "dvis_conv_x3_image" : "dvis_conv1x1_x3");
+  }
 #define DVIS_CX_LAUNCH(NBV, IKV)                                                                              \
   {                                                                                                           \
     static DvisLdsOptIn opted;                                                                                \

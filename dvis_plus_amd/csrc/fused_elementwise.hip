@@ -714,6 +714,42 @@ __global__ __launch_bounds__(1024) void group_norm_affine_kernel(const float *__
   }
 }
 
+// The tail of group_norm_affine_kernel on statistics a convolution's epilogue left behind (csrc/conv1x1_x3.hip, CxArgs::gn_part):
+// per (sample, group) `slots` partial (sum, sum of squares) pairs, one per 32 pixels.  One wave per (sample, group): lane l adds
+// the slots l, l + 64, ... in that order, then a fixed tree over the lanes — a function of the sample's data alone.
+__global__ __launch_bounds__(64) void group_norm_finalize_kernel(const double *__restrict__ part, const float *__restrict__ gamma,
+                                                                 const float *__restrict__ beta, float *__restrict__ scale,
+                                                                 float *__restrict__ shift, int C, int G, int slots, long long HW,
+                                                                 float eps) {
+  const int Cg = C / G;
+  const int n = blockIdx.x / G, g = blockIdx.x - n * G;
+  const long long count = (long long)Cg * HW;
+  const double2 *pp = reinterpret_cast<const double2 *>(part) + (size_t)blockIdx.x * slots;
+  double ts = 0.0, tq = 0.0;
+  for (int i = threadIdx.x; i < slots; i += 64) {
+    const double2 v = pp[i];
+    ts += v.x;
+    tq += v.y;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ts += __shfl_down(ts, o);
+    tq += __shfl_down(tq, o);
+  }
+  ts = __shfl(ts, 0);
+  tq = __shfl(tq, 0);
+  if (threadIdx.x < Cg) {
+    const double mean = ts / (double)count;
+    double var = tq / (double)count - mean * mean;
+    var = var < 0.0 ? 0.0 : var;
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    const int c = g * Cg + threadIdx.x;
+    const float a = rstd * (gamma ? gamma[c] : 1.f);
+    scale[(size_t)n * C + c] = a;
+    shift[(size_t)n * C + c] = (beta ? beta[c] : 0.f) - (float)mean * a;
+  }
+}
+
 // x[plane][i] = relu?(x * scale[plane] + shift[plane]); grid.x = planes * chunks_per_plane
 __global__ __launch_bounds__(256) void scale_shift_act_kernel(float *__restrict__ x, const float *__restrict__ scale,
                                                               const float *__restrict__ shift, int HW4, int chunks, int relu) {
@@ -754,6 +790,19 @@ DVIS_EXPORT int dvis_group_norm_affine(const float *x, const float *gamma, const
   hipLaunchKernelGGL(group_norm_affine_kernel, dim3((unsigned)(N * G)), dim3(1024), 0, (hipStream_t)stream, x, gamma, beta,
                      scale, shift, C, G, (long long)HW, eps, vec);
   return dvis_check_launch("group_norm_affine_kernel");
+}
+
+DVIS_EXPORT int dvis_group_norm_finalize(const double *part, const float *gamma, const float *beta, float *scale, float *shift,
+                                         int64_t N, int C, int G, int64_t HW, float eps, void *stream) {
+  DVIS_REQUIRE(N >= 0 && C > 0 && G > 0 && HW > 0 && C % G == 0 && HW % 32 == 0 && HW / 32 < (1ll << 31),
+               "group_norm_finalize: bad sizes (C=%d G=%d)", C, G);
+  if (N == 0) return DVIS_OK;
+  DVIS_REQUIRE(part && scale && shift && ((uintptr_t)part & 15) == 0, "group_norm_finalize: null / unaligned pointer");
+  DVIS_REQUIRE(C / G <= 64, "group_norm_finalize: at most 64 channels per group");
+  DVIS_REQUIRE(N * G < (1ll << 31), "group_norm_finalize: too many groups");
+  hipLaunchKernelGGL(group_norm_finalize_kernel, dim3((unsigned)(N * G)), dim3(64), 0, (hipStream_t)stream, part, gamma, beta, scale,
+                     shift, C, G, (int)(HW / 32), (long long)HW, eps);
+  return dvis_check_launch("group_norm_finalize_kernel");
 }
 
 DVIS_EXPORT int dvis_scale_shift_act(float *x, const float *scale, const float *shift, int64_t planes, int64_t HW, int relu,

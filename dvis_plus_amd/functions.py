@@ -1868,8 +1868,47 @@ def _conv_x3_chunks(N, Ci, Co, HW_in, HW_out):
     return max(1, min(N, (2 ** 31 - 1) // per))
 
 
-def conv1x1_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None):
-    """relu?(conv1x1(x, weight)[:, :, ::stride, ::stride] + bias[c] + res) through dvis_conv1x1_x3."""
+PD_GN_FOLD = os.environ.get("DVIS_PD_GN_FOLD", "1") != "0"
+
+
+def gn_fold_ok(norm, K, HW):
+    """May a split-f16 convolution with K output channels on maps of HW pixels leave the statistics of the GroupNorm `norm` behind
+    (conv1x1_x3 / conv_x3_image, gn=norm)?  A wave's 32 pixels in one frame, a group = the 8 channels of one accumulator row pair."""
+    return bool(PD_GN_FOLD and isinstance(norm, torch.nn.GroupNorm) and norm.num_channels == K
+                and native.lib().dvis_conv_x3_gn_fold_supported(K, norm.num_groups, HW))
+
+
+def affine_in_ok(x, weight):
+    """May conv1x1_x3 apply a per-plane (scale, shift) (+ ReLU) to x as it reads it (affine=...)?  256 -> K % 256 == 0 channels, whole
+    waves per frame."""
+    return bool(PD_GN_FOLD and conv1x1_x3_ok(x, weight) and x.shape[1] == 256 and x.shape[0] > 0
+                and native.lib().dvis_conv_x3_gn_fold_supported(weight.shape[0], weight.shape[0] // 8, x.shape[2] * x.shape[3]))
+
+
+def _gn_partials(N, K, HW, device):
+    """The side buffer of a gn= launch: (frame, group, 32-pixel slot, (sum, sum of squares)) in fp64, every element written."""
+    return torch.empty((N, K // 8, HW // 32, 2), dtype=torch.float64, device=device)
+
+
+def _gn_finalize(part, norm, N, K, HW):
+    """group_norm_affine's (scale, shift) from the partial sums of a gn= launch."""
+    scale = torch.empty(N * K, dtype=torch.float32, device=part.device)
+    shift = torch.empty(N * K, dtype=torch.float32, device=part.device)
+    with torch.cuda.device(part.device):
+        native.check(native.lib().dvis_group_norm_finalize(
+            native.dev_ptr(part, "partials"), None if norm.weight is None else native.dev_ptr(norm.weight.detach(), "gamma"),
+            None if norm.bias is None else native.dev_ptr(norm.bias.detach(), "beta"), native.dev_ptr(scale, "scale"),
+            native.dev_ptr(shift, "shift"), N, K, norm.num_groups, HW, float(norm.eps), native.stream_ptr(part.device)),
+            "dvis_group_norm_finalize")
+    return scale, shift
+
+
+def conv1x1_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None, affine=None, affine_relu=False, gn=None):
+    """relu?(conv1x1(x, weight)[:, :, ::stride, ::stride] + bias[c] + res) through dvis_conv1x1_x3.
+    affine = (scale, shift) per plane of x (``group_norm_affine``): x is read as affine_relu?(x * scale + shift), the arithmetic of
+    ``scale_shift_act_`` without its pass over the map (``affine_in_ok``).
+    gn: a GroupNorm of the OUTPUT — returns (out, (scale, shift)) with the pair ``group_norm_affine(out, gn)`` returns, its
+    statistics taken from the epilogue's registers where ``gn_fold_ok`` holds, by that kernel otherwise."""
     N, Ci, H, W = x.shape
     Co = weight.shape[0]
 
@@ -1879,6 +1918,9 @@ def conv1x1_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None):
     OH, OW = (H + stride - 1) // stride, (W + stride - 1) // stride
     out = torch.empty((N, Co, OH, OW), dtype=torch.float32, device=x.device)
     step = _conv_x3_chunks(N, Ci, Co, H * W, OH * OW)
+    if affine is not None and not (affine_in_ok(x, weight) and stride == 1 and gn is None):
+        raise RuntimeError("conv1x1_x3: this launch takes no input affine (see affine_in_ok); apply scale_shift_act_ first")
+    part = _gn_partials(N, Co, OH * OW, x.device) if gn is not None and N > 0 and gn_fold_ok(gn, Co, OH * OW) else None
     with torch.cuda.device(x.device):
         for i in range(0, N, step):
             n = min(step, N - i)
@@ -1886,9 +1928,13 @@ def conv1x1_x3(x, weight, bias=None, res=None, relu=False, stride=1, xexp=None):
                 native.dev_ptr(x[i:i + n], "x"), ctypes.c_void_p(buf.data_ptr()),
                 None if bias is None else native.dev_ptr(bias.detach(), "bias"),
                 None if res is None else native.dev_ptr(res[i:i + n], "res"), native.dev_ptr(out[i:i + n], "out"), n, Ci, Co, H, W,
-                stride, X3_CONV_XEXP if xexp is None else xexp, wexp, 1 if relu else 0, native.stream_ptr(x.device)),
-                "dvis_conv1x1_x3")
-    return out
+                stride, X3_CONV_XEXP if xexp is None else xexp, wexp, 1 if relu else 0, native.stream_ptr(x.device),
+                None if affine is None else native.dev_ptr(affine[0].reshape(N, Ci)[i:i + n], "scale"),
+                None if affine is None else native.dev_ptr(affine[1].reshape(N, Ci)[i:i + n], "shift"), 1 if affine_relu else 0,
+                None if part is None else native.dev_ptr(part[i:i + n], "partials")), "dvis_conv1x1_x3")
+    if gn is None:
+        return out
+    return out, (_gn_finalize(part, gn, N, Co, OH * OW) if part is not None else group_norm_affine(out, gn))
 
 
 X3_DUAL = os.environ.get("DVIS_X3_DUAL", "1") != "0"
@@ -2018,10 +2064,10 @@ def upsample_add_image(lateral, top, lat_affine=None, oexp=None):
     return img
 
 
-def conv_x3_image(src, weight, bias=None, res=None, relu=False, stride=1, out_image=False, oexp=None, xexp=None):
+def conv_x3_image(src, weight, bias=None, res=None, relu=False, stride=1, out_image=False, oexp=None, xexp=None, gn=None):
     """relu?(conv2d(src, weight, stride, padding = k // 2) + bias + res) through dvis_conv_x3_image: `src` an OperandImage or an
     (N, C, H, W) fp32 map (then out_image must be set), weight (K, C, 1, 1) or (K, C, 3, 3); returns an OperandImage (out_image) or
-    the (N, K, OH, OW) fp32 map."""
+    the (N, K, OH, OW) fp32 map.  gn (image in, map out): as in ``conv1x1_x3`` — returns (out, (scale, shift))."""
     lib = native.lib()
     from_img = isinstance(src, OperandImage)
     if not (from_img or out_image):
@@ -2046,6 +2092,9 @@ def conv_x3_image(src, weight, bias=None, res=None, relu=False, stride=1, out_im
     else:
         out = torch.empty((N, K, OH, OW), dtype=torch.float32, device=dev)
     step = _image_chunks(N, C, K, H, W, OH, OW)
+    if gn is not None and not (from_img and not out_image):
+        raise ValueError("conv_x3_image: gn needs an operand image in and an fp32 map out")
+    part = _gn_partials(N, K, OH * OW, dev) if gn is not None and N > 0 and gn_fold_ok(gn, K, OH * OW) else None
     with torch.cuda.device(dev):
         for i in range(0, N, step):
             n = min(step, N - i)
@@ -2054,8 +2103,10 @@ def conv_x3_image(src, weight, bias=None, res=None, relu=False, stride=1, out_im
                 ctypes.c_void_p(buf.data_ptr()), None if bias is None else native.dev_ptr(bias.detach(), "bias"),
                 None if res is None else native.dev_ptr(res[i:i + n], "res"), None if out_image else native.dev_ptr(out[i:i + n], "out"),
                 ctypes.c_void_p(out.images(i, n).data_ptr()) if out_image else None, n, C, K, H, W, stride, taps, xe, wexp, oe, 1 if relu else 0,
-                native.stream_ptr(dev)), "dvis_conv_x3_image")
-    return out
+                native.stream_ptr(dev), None if part is None else native.dev_ptr(part[i:i + n], "partials")), "dvis_conv_x3_image")
+    if gn is None:
+        return out
+    return out, (_gn_finalize(part, gn, N, K, OH * OW) if part is not None else group_norm_affine(out, gn))
 
 
 X3_BNECK = os.environ.get("DVIS_X3_BNECK", "1") != "0"

@@ -70,6 +70,7 @@ SIGNATURES = {
     "dvis_bias_relu_maxpool": (_i, [_p, _p, _p, _i64, _i, _i, _i, _p]),
     "dvis_group_norm_affine": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i64, _f, _p]),
     "dvis_scale_shift_act": (_i, [_p, _p, _p, _i64, _i64, _i, _p]),
+    "dvis_group_norm_finalize": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i64, _f, _p]),
     "dvis_upsample_add_affine": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "dvis_upsample_add": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "dvis_dwconv3x3_tokens": (_i, [_p, _p, _i64, _i, _i, _i, _i, _p, _p, _i, _p]),
@@ -119,7 +120,8 @@ SIGNATURES = {
     "dvis_conv1x1_x3_supported": (_i, [_i, _i, _i64, _i64, _i64]),
     "dvis_conv1x1_x3_packed_bytes": (_i64, [_i, _i]),
     "dvis_conv1x1_x3_pack": (_i, [_p, _i, _i, _i, _p, _p]),
-    "dvis_conv1x1_x3": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "dvis_conv_x3_gn_fold_supported": (_i, [_i, _i, _i64]),
+    "dvis_conv1x1_x3": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p]),
     "dvis_conv1x1_x3_dual": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dvis_conv3x3_x3_packed_bytes": (_i64, [_i, _i]),
     "dvis_conv3x3_x3_pack": (_i, [_p, _i, _i, _i, _p, _p]),
@@ -132,7 +134,7 @@ SIGNATURES = {
     "dvis_conv1x1_x3_image": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dvis_conv_x3_image_bytes": (_i64, [_i64, _i, _i, _i]),
     "dvis_conv_x3_pack_image": (_i, [_p, _i, _i, _i, _i, _p, _p]),
-    "dvis_conv_x3_image": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "dvis_conv_x3_image": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dvis_upsample_add_image": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dvis_gemm_num_configs": (_i, []),
     "dvis_gemm_pick_config": (_i, [_i, _i, _i, _i]),

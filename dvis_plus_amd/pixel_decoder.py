@@ -418,8 +418,17 @@ class ConvNorm(nn.Conv2d):
         super().__init__(*args, **kwargs)
         self.norm, self.activation = norm, activation
 
-    def conv(self, x):
-        if self.kernel_size == (1, 1) and self.stride == (1, 1) and self.groups == 1 and self.padding == (0, 0):
+    def _plain_1x1(self):
+        return self.kernel_size == (1, 1) and self.stride == (1, 1) and self.groups == 1 and self.padding == (0, 0)
+
+    def affine_input_ok(self, x):
+        """May forward take `x` un-normalised, with its GroupNorm (+ ReLU) as in_affine (applied as the convolution reads x)?"""
+        return self._plain_1x1() and torch.is_tensor(x) and Fn.affine_in_ok(x, self.weight)
+
+    def conv(self, x, in_affine=None):
+        if in_affine is not None:
+            return Fn.conv1x1_x3(x, self.weight, self.bias, affine=in_affine[:2], affine_relu=in_affine[2])
+        if self._plain_1x1():
             return Fn.conv1x1(x, self.weight, self.bias)
         if self.kernel_size == (3, 3) and self.stride == (1, 1) and self.padding == (1, 1) and self.dilation == (1, 1) \
                 and self.groups == 1 and x.is_cuda and not torch.is_grad_enabled():
@@ -430,6 +439,9 @@ class ConvNorm(nn.Conv2d):
         """(conv(x), (scale, shift)) with forward(x) == conv(x) * scale + shift per plane, for a GroupNorm without
         activation whose application the consumer fuses (Fn.upsample_add); (forward(x), None) when that does not apply."""
         if isinstance(self.norm, nn.GroupNorm) and self.activation is None:
+            if self._plain_1x1() and Fn.conv1x1_x3_ok(x, self.weight) \
+                    and Fn.gn_fold_ok(self.norm, self.out_channels, x.shape[2] * x.shape[3]):
+                return Fn.conv1x1_x3(x, self.weight, self.bias, gn=self.norm)    # the statistics from the convolution's epilogue
             y = self.conv(x)
             aff = Fn.group_norm_affine(y, self.norm)
             if aff is not None:
@@ -443,15 +455,26 @@ class ConvNorm(nn.Conv2d):
             and ((self.kernel_size == (3, 3) and self.padding == (1, 1)) or (self.kernel_size == (1, 1) and self.padding == (0, 0))) \
             and C == self.in_channels and Fn.x3_images_ok(N, C, self.out_channels, H, W, device, taps=self.kernel_size[0] ** 2)
 
-    def forward(self, x):
+    def forward(self, x, in_affine=None, defer_to=None):
+        """in_affine = (scale, shift, relu): x is a map whose GroupNorm (+ ReLU) is still to be applied (affine_input_ok).
+        defer_to: the ConvNorm that is this output's ONLY reader — where it can take the GroupNorm (+ ReLU) of this layer as its
+        in_affine, returns (un-normalised map, (scale, shift, relu)) instead of the map."""
+        aff = None
+        gn_relu = isinstance(self.norm, nn.GroupNorm) and self.activation in (None, F.relu)
         if isinstance(x, Fn.OperandImage):
-            x = Fn.conv_x3_image(x, self.weight, self.bias)
+            if gn_relu:        # (the statistics from the convolution's epilogue where that form serves the shape)
+                x, aff = Fn.conv_x3_image(x, self.weight, self.bias, gn=self.norm)
+            else:
+                x = Fn.conv_x3_image(x, self.weight, self.bias)
         else:
-            x = self.conv(x)
-        if isinstance(self.norm, nn.GroupNorm) and self.activation in (None, F.relu):
+            x = self.conv(x, in_affine)
+        if gn_relu:
             # statistics in one read, normalisation (+ReLU) in one in-place pass (torch: moments, apply, clamp)
-            aff = Fn.group_norm_affine(x, self.norm)
+            if aff is None:
+                aff = Fn.group_norm_affine(x, self.norm)
             if aff is not None:
+                if defer_to is not None and defer_to.affine_input_ok(x):
+                    return x, (aff[0], aff[1], self.activation is not None)
                 return Fn.scale_shift_act_(x, aff[0], aff[1], relu=self.activation is not None)
         if self.norm is not None:
             x = self.norm(x)
@@ -561,6 +584,7 @@ class MSDeformAttnPixelDecoder(nn.Module):
                     out.append(tokens[-1].transpose(1, 2).reshape(bs, -1, h, w))  # a strided view, no copy
                 start += h * w
             with Fn.x3_stage("mask_path"):        # lateral 1x1 -> top-down add -> 3x3 output conv -> mask_features 1x1
+                deferred = None            # the last output convolution's GroupNorm + ReLU, left to mask_features' load path
                 for idx, f in enumerate(self.in_features[:self.num_fpn_levels][::-1]):
                     x = features[f].float().contiguous()      # NCHW for the fused FPN path (no-op for the R50's maps)
                     cur_fpn, affine = self.lateral_convs[idx].conv_and_affine(x)    # GroupNorm applied inside upsample_add
@@ -568,12 +592,18 @@ class MSDeformAttnPixelDecoder(nn.Module):
                     if cur_fpn.is_cuda and cur_fpn.dtype == torch.float32 and cur_fpn.is_contiguous() and out[-1].dtype == torch.float32 \
                             and oc.image_input_ok(*cur_fpn.shape, cur_fpn.device):
                         # the top-down sum as an operand image: the 3x3 output convolution reads pre-split fragments (csrc/conv1x1_x3.hip)
-                        out.append(oc(Fn.upsample_add_image(cur_fpn, out[-1], affine)))
+                        # out[-1] of the LAST level past the multi-scale features has one reader, mask_features: its normalisation
+                        # can wait for that read (an inner level's is read by the next upsample_add, a multi-scale map by the decoder)
+                        last = idx + 1 == self.num_fpn_levels and len(out) >= self.maskformer_num_feature_levels
+                        y = oc(Fn.upsample_add_image(cur_fpn, out[-1], affine), defer_to=self.mask_features if last else None)
+                        if isinstance(y, tuple):
+                            y, deferred = y
+                        out.append(y)
                     else:
                         out.append(oc(Fn.upsample_add(cur_fpn, out[-1], affine)))
                 multi_scale_features = TokenMaps(out[:self.maskformer_num_feature_levels])
                 multi_scale_features.tokens = tokens[:self.maskformer_num_feature_levels]
-                return self.mask_features(out[-1]), out[0], multi_scale_features
+                return self.mask_features(out[-1], in_affine=deferred), out[0], multi_scale_features
 
 
 class TokenMaps(list):

@@ -442,6 +442,10 @@ int dvis_group_norm_affine(const float *x, const float *gamma, const float *beta
                            int C, int G, int64_t HW, float eps, void *stream);
 int dvis_scale_shift_act(float *x, const float *scale, const float *shift, int64_t planes, int64_t HW, int relu,
                          void *stream);
+/* dvis_group_norm_affine's (scale, shift) from the partial sums a convolution left in `part` (dvis_conv1x1_x3 / dvis_conv_x3_image,
+ * gn_part: (N, G, HW / 32, 2) doubles) instead of a read of the map: the same formula and casts; HW % 32 == 0, C / G <= 64. */
+int dvis_group_norm_finalize(const double *part, const float *gamma, const float *beta, float *scale, float *shift, int64_t N, int C,
+                             int G, int64_t HW, float eps, void *stream);
 int dvis_upsample_add_affine(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top,
                              float *out, int64_t planes, int H, int W, int h, int w, void *stream);
 
@@ -709,8 +713,17 @@ int64_t dvis_x3_ffn_packed_bytes(int K, int H, int N);
 int dvis_conv1x1_x3_supported(int C, int K, int64_t N, int64_t HW_in, int64_t HW_out);
 int64_t dvis_conv1x1_x3_packed_bytes(int C, int K);
 int dvis_conv1x1_x3_pack(const float *w, int K, int C, int wexp, void *packed, void *stream);
+/* The GroupNorm around a convolution, folded into the launch (the pixel decoder's mask path; all NULL / 0 = the plain launch):
+ *   in_scale / in_shift (N * C)  x is read as in_relu?(x * in_scale[n*C + c] + in_shift[n*C + c]): dvis_scale_shift_act's arithmetic
+ *                                on the way into the split, without its pass over the map; stride 1, C = 256;
+ *   gn_part                      N * (K / 8) * (H * W / 32) * 2 doubles: per (image, group of 8 channels, 32 pixels) the sum and
+ *                                the sum of squares of y as stored — dvis_group_norm_finalize turns them into GroupNorm(K / 8, K)'s
+ *                                (scale, shift).  Every element is written; a function of the image's data alone.
+ * Either needs dvis_conv_x3_gn_fold_supported(K, K / 8, H * W): K % 256 == 0, H * W % 32 == 0; one of the two per launch. */
+int dvis_conv_x3_gn_fold_supported(int K, int G, int64_t HW);
 int dvis_conv1x1_x3(const float *x, const void *packed, const float *bias, const float *res, float *y, int N, int C, int K, int H,
-                    int W, int stride, int xexp, int wexp, int relu, void *stream);
+                    int W, int stride, int xexp, int wexp, int relu, void *stream, const float *in_scale, const float *in_shift,
+                    int in_relu, double *gn_part);
 /* The last 1x1 convolution of a down-sampling bottleneck TOGETHER with its shortcut (detectron2 BottleneckBlock with a
  * projection shortcut, SURVEY.md App. B: out = relu(conv3(a) + shortcut(x))): one accumulation over the concatenated channels
  * [a (N, C, H, W) | x2 (N, C2, H2, W2) sampled with stride2], `packed` = dvis_conv1x1_x3_pack of the (K, C + C2) matrix
@@ -755,7 +768,8 @@ int dvis_conv1x1_x3_image(const float *x, const void *packed, const float *bias,
 int64_t dvis_conv_x3_image_bytes(int64_t N, int C, int H, int W);
 int dvis_conv_x3_pack_image(const float *w, int K, int C, int taps, int wexp, void *packed, void *stream);
 int dvis_conv_x3_image(const void *ximg, const float *x, const void *packed, const float *bias, const float *res, float *y, void *image,
-                       int N, int C, int K, int H, int W, int stride, int taps, int xexp, int wexp, int oexp, int relu, void *stream);
+                       int N, int C, int K, int H, int W, int stride, int taps, int xexp, int wexp, int oexp, int relu, void *stream,
+                       double *gn_part);      /* gn_part: as dvis_conv1x1_x3 (image in, fp32 map out), or NULL */
 int dvis_upsample_add_image(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top, void *image, int N,
                             int C, int H, int W, int h, int w, int oexp, void *stream);
 int dvis_x3_ffn_pack(const float *W1, int64_t ldw1, const float *W2, int64_t ldw2, int K, int H, int N, int w1exp, int w2exp,
