@@ -663,6 +663,129 @@ class AttentionFunction(Function):
         return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None
 
 
+MASKED_ATTENTION_BACKWARD_MAX_QUERIES = 256
+MASKED_ATTENTION_BACKWARD_MAX_KEYS = 65536
+MaskedAttentionBackwardPlan = collections.namedtuple("MaskedAttentionBackwardPlan",
+                                                     "key_tile query_tile n_key_tiles threads lds_bytes")
+
+
+def masked_attention_backward_plan(Lq, Lk, d):
+    """How ``masked_attention_backward`` cuts Lq queries and Lk keys of head dim d: MaskedAttentionBackwardPlan(key_tile, query_tile,
+    n_key_tiles, threads, lds_bytes) — keys per workgroup, queries per chunk inside it, workgroups per (batch entry, head), threads per
+    workgroup, dynamic LDS — asked of the library, whose launch uses the same function."""
+    plan = (ctypes.c_int32 * 5)()
+    native.check(native.lib().dvis_masked_attention_backward_plan(int(Lq), int(Lk), int(d), plan),
+                 "dvis_masked_attention_backward_plan")
+    return MaskedAttentionBackwardPlan(*plan)
+
+
+def _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_count, out=None):
+    """The contract of csrc/masked_attention_backward.hip, checked on the host before anything is launched.  Returns the mask as
+    uint8."""
+    tensors = [("q", q), ("k", k), ("v", v)] + [(n, t) for n, t in (("grad_out", grad_out), ("out", out)) if t is not None]
+    for name, t in tensors:
+        if not t.is_cuda or t.dim() != 3:
+            raise RuntimeError(f"masked_attention_backward: {name} must be a GPU (L, B, C) tensor")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"masked_attention_backward: {name} must be float32 (got {t.dtype})")
+        if t.stride(2) != 1:
+            raise RuntimeError(f"masked_attention_backward: {name} must have inner stride 1 (got {t.stride(2)})")
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or any(t is not None and t.shape != q.shape for t in (grad_out, out)):
+        raise RuntimeError("masked_attention_backward: inconsistent q / k / v / grad_out / out shapes")
+    if C % nheads or C // nheads not in (32, 64):
+        raise RuntimeError(f"masked_attention_backward: head dim must be 32 or 64 (got C={C} over {nheads} heads)")
+    if Lq < 1 or Lk < 1:
+        raise RuntimeError(f"masked_attention_backward: needs Lq >= 1 and Lk >= 1 (got Lq={Lq}, Lk={Lk})")
+    if Lq > MASKED_ATTENTION_BACKWARD_MAX_QUERIES:
+        raise RuntimeError(f"masked_attention_backward: serves at most {MASKED_ATTENTION_BACKWARD_MAX_QUERIES} queries (got Lq={Lq})")
+    if Lk > MASKED_ATTENTION_BACKWARD_MAX_KEYS:
+        raise RuntimeError(f"masked_attention_backward: serves at most {MASKED_ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
+    if mask is None:
+        return None
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    if mask.dtype != torch.uint8 or mask.shape != (B, Lq, Lk) or not mask.is_cuda:
+        raise RuntimeError(f"masked_attention_backward: mask must be a uint8 / bool GPU tensor of shape (B, Lq, Lk) = {(B, Lq, Lk)} "
+                           f"(got {mask.dtype} {tuple(mask.shape)})")
+    if allowed_count is None:
+        raise RuntimeError("masked_attention_backward: a mask needs its allowed_count (int32 (B, Lq), from attn_mask)")
+    if allowed_count.dtype != torch.int32 or allowed_count.shape != (B, Lq) or not allowed_count.is_cuda:
+        raise RuntimeError(f"masked_attention_backward: allowed_count must be an int32 GPU tensor of shape (B, Lq) = {(B, Lq)}")
+    return mask
+
+
+def masked_attention_backward(q, k, v, grad_out, nheads, mask=None, allowed_count=None, out=None):
+    """Gradients of ``masked_attention(q, k, v, nheads, mask, allowed_count)`` for the upstream gradient ``grad_out``
+    (csrc/masked_attention_backward.hip): q / grad_out (Lq, B, C), k / v (Lk, B, C) float32 GPU tensors with unit inner stride and
+    arbitrary row / batch strides, head dim 32 or 64, Lq <= 256, Lk <= 65536; mask uint8 / bool (B, Lq, Lk) with 1 = blocked and its
+    allowed_count int32 (B, Lq) (a row with count 0 ignores its mask) -> (dq (Lq, B, C), dk (Lk, B, C), dv (Lk, B, C)), contiguous.
+    ``out`` — the forward's result for the same arguments — is accepted and checked for its shape but not read: the kernel takes
+    D = rowsum(P o dP) from the probabilities it recomputes (csrc/masked_attention_backward.hip says why), so no forward call is
+    needed either.  A blocked key gets no contribution from the query that blocks it.  Exact fp32, no atomics:
+    the same bits on every call, and a batch entry's bits do not depend on B.  Anything outside the contract raises before a
+    launch; there is no torch formulation behind it for GPU tensors."""
+    mask = _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_count, out)
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    d = C // nheads
+    dev = q.device
+    dq = torch.empty((Lq, B, C), dtype=torch.float32, device=dev)
+    dk = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    dv = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    if B == 0:
+        return dq, dk, dv
+    lib = native.lib()
+    ws = torch.empty((lib.dvis_masked_attention_backward_ws_bytes(B * nheads, Lq, Lk, d) // 4,), dtype=torch.float32, device=dev)
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        rc = lib.dvis_masked_attention_backward(
+            ptr(q), _strides3(q, B, C, d), ptr(k), _strides3(k, B, C, d), ptr(v), _strides3(v, B, C, d), ptr(grad_out),
+            _strides3(grad_out, B, C, d),
+            native.dev_ptr(mask, "mask") if mask is not None else None,
+            native.dev_ptr(allowed_count, "allowed_count") if mask is not None else None, ptr(dq), ptr(dk), ptr(dv), B, nheads, Lq, Lk,
+            d, 1.0 / (d ** 0.5), ptr(ws), native.stream_ptr(dev))
+    native.check(rc, "dvis_masked_attention_backward")
+    return dq, dk, dv
+
+
+class MaskedAttentionFunction(Function):
+    """``masked_attention`` under autograd: the forward kernel as it is, csrc/masked_attention_backward.hip for q, k and v; the mask
+    and its counts get no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nheads, mask, allowed_count):
+        ctx.save_for_backward(q, k, v, mask, allowed_count)       # (not the output: the backward recomputes what it needs)
+        ctx.nheads = nheads
+        return _attention_kernel(q, k, v, nheads, mask, allowed_count)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, mask, allowed_count = ctx.saved_tensors
+        # the kernel's view contract (AttentionFunction.backward says what can miss it): copy
+        B = grad_out.shape[1]
+        if grad_out.stride(2) != 1 or grad_out.data_ptr() % 16 or grad_out.stride(0) % 4 or (B > 1 and grad_out.stride(1) % 4):
+            grad_out = grad_out.contiguous()
+        dq, dk, dv = masked_attention_backward(q, k, v, grad_out, ctx.nheads, mask, allowed_count)
+        need = ctx.needs_input_grad
+        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None
+
+
+def masked_attention(q, k, v, nheads, mask=None, allowed_count=None):
+    """``attention(q, k, v, nheads, mask, allowed_count)`` — the same forward kernel, the same bits — that is differentiable WITH a
+    mask and over long key sequences: an input that requires grad routes the call through MaskedAttentionFunction (backward
+    csrc/masked_attention_backward.hip: Lq <= 256, Lk <= 65536, head dim 32 or 64; a mask needs its allowed_count).  The
+    cross-attention of the masked-attention decoder in training.  CPU tensors: cpu_ops.attention and torch's own autograd."""
+    if _on_cpu(q, k, v):
+        return cpu_ops.attention(q, k, v, nheads, mask, allowed_count)
+    if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
+        mask = _masked_attention_backward_check(q, k, v, None, nheads, mask, allowed_count)
+        return MaskedAttentionFunction.apply(q, k, v, nheads, mask, allowed_count)
+    return _attention_kernel(q, k, v, nheads, mask, allowed_count)
+
+
 def vps_argmax(mask_logits_kthw, scores, first_resize_size, img_size, out_hw):
     """Fused panoptic arg-max (see dvis_vps_argmax).  mask_logits_kthw: float32 GPU (K, T, h, w) view whose last two
     dims are contiguous; scores float32 (K,).  Returns ids int32 (T,H,W), conf bool (T,H,W), areas int32 (3, K)."""

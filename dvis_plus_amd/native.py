@@ -49,6 +49,9 @@ SIGNATURES = {
     "dvis_attention_forward_k": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _i]),
     "dvis_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "dvis_attention_backward_threads": (_i, [_i]),
+    "dvis_masked_attention_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "dvis_masked_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p]),
+    "dvis_masked_attention_backward_plan": (_i, [_i, _i, _i, _p]),
     "dvis_add_layernorm": (_i, [_p, _p, _i64, _p, _p, _p, _i64, _i, _f, _p]),
     "dvis_add_layernorm_pos": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i, _f, _p]),
     "dvis_bias_act": (_i, [_p, _p, _p, _i64, _i, _i64, _i, _p]),

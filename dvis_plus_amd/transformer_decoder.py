@@ -17,6 +17,10 @@ Inference-only re-organisation for MI355X (same numbers as the reference's eval 
     full-resolution logits are only produced on request, class logits only for the last layer
     (the reference computes and discards the others in eval);
   * the "row blocked everywhere" reset needs no host sync (allowed_count travels with the mask).
+
+Under ``.train()`` all four classes run ``_train_layers`` instead: the reference's training forward (L + 1 predictions,
+``aux_outputs``, the (b t) -> (b, t) split by ``num_frames``) as torch ops under autograd around ``Fn.masked_attention``
+(cross-attention; backward csrc/masked_attention_backward.hip), ``Fn.attention`` (self-attention) and ``Fn.mask_logits``.
 """
 import torch
 import torch.nn.functional as F
@@ -290,10 +294,104 @@ class _MaskedDecoderBase(nn.Module):
         masks = Fn.mask_logits(self.mask_embed(dec).contiguous(), mask_features) if need_masks else None
         return dec, logits, masks
 
+    # ---- training (video_mask2former_transformer_decoder.py:258-379): torch ops under autograd around the attention kernels --------
+
+    @staticmethod
+    def _train_mlp(mlp, x):
+        if not isinstance(mlp, MLP):
+            return mlp(x)
+        for j, lin in enumerate(mlp.layers):
+            x = F.linear(x, lin.weight, lin.bias)
+            x = torch.relu(x) if j < mlp.num_layers - 1 else x
+        return x
+
+    def _train_layers(self, x, mask_features):
+        """The training forward of the layers and of the heads on the learnable queries and after every layer.
+        x: 3 feature maps (N, C, h_l, w_l), low-res first; mask_features (N, Cm, H, W).  Returns (output (Q, N, C) un-normed after
+        the last layer, its decoder_norm as (N, Q, C), class logits [L + 1 x (N, Q, K + 1)], mask logits [L + 1 x (N, Q, H, W)]).
+
+        Nothing weight-derived is cached: every layer's K / V projection is an F.linear on the live parameters, so the gradient
+        reaches them, input_proj, level_embed and the input maps.  Cross-attention is Fn.masked_attention (forward kernel,
+        csrc/masked_attention_backward.hip), self-attention Fn.attention (<= 256 keys: csrc/attention_backward.hip); CPU tensors
+        take the torch formulations of both.  A layer's attention mask comes from Fn.attn_mask on the DETACHED embedding (the
+        reference detaches at :377).  The mask logits of all L + 1 predictions are ONE Fn.mask_logits call with (L + 1) Q rows per
+        frame while mask_features needs no gradient, one call per prediction when it does (that gradient contracts over at most
+        256 rows, Fn._mask_logits_grad_features).  No graph capture here."""
+        C = self.decoder_norm.weight.shape[0]
+        N = x[0].shape[0]
+        nh, L = self.num_heads, self.num_layers
+        size_list, src, pos = [], [], []
+        for lvl in range(self.num_feature_levels):
+            h, w = x[lvl].shape[-2:]
+            size_list.append((h, w))
+            proj = self.input_proj[lvl]
+            m = F.conv2d(x[lvl], proj.weight, proj.bias) if isinstance(proj, nn.Conv2d) else proj(x[lvl])
+            src.append((m.flatten(2) + self.level_embed.weight[lvl][None, :, None]).permute(2, 0, 1))       # (hw, N, C)
+            pos.append(self.pe_layer.compute(h, w, x[lvl].device).to(m.dtype).flatten(2).permute(2, 0, 1))   # (hw, 1, C)
+        query_embed = self.query_embed.weight.unsqueeze(1)                                      # (Q, 1, C) broadcasts
+        output = self.query_feat.weight.unsqueeze(1).repeat(1, N, 1)
+        feats = mask_features.detach()
+        logits, embs = [], []
+
+        def heads(output):
+            dec = self.decoder_norm(output).transpose(0, 1)                                     # (N, Q, C)
+            logits.append(F.linear(dec, self.class_embed.weight, self.class_embed.bias))
+            embs.append(self._train_mlp(self.mask_embed, dec))
+            return dec
+
+        dec = heads(output)
+        for i in range(L):
+            lvl = i % self.num_feature_levels
+            with torch.no_grad():
+                mask, allowed = Fn.attn_mask(embs[-1].detach().contiguous(), feats, size_list[lvl])
+            if self.debug_masks is not None:     # rows blocked everywhere attend everywhere (…decoder.py:296)
+                self.debug_masks.append(mask.bool() & (allowed > 0)[..., None])
+            ca = self.transformer_cross_attention_layers[i]
+            W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
+            att = Fn.masked_attention(F.linear(output + query_embed, W[:C], b[:C]), F.linear(src[lvl] + pos[lvl], W[C:2 * C], b[C:2 * C]),
+                                      F.linear(src[lvl], W[2 * C:], b[2 * C:]), nh, mask, allowed)
+            op = ca.multihead_attn.out_proj
+            output = ca.norm(output + F.linear(att, op.weight, op.bias))
+            sa = self.transformer_self_attention_layers[i]
+            W, b = sa.self_attn.in_proj_weight, sa.self_attn.in_proj_bias
+            qk = F.linear(output + query_embed, W[:2 * C], b[:2 * C])
+            att = Fn.attention(qk[..., :C], qk[..., C:], F.linear(output, W[2 * C:], b[2 * C:]), nh)
+            output = sa.norm(output + F.linear(att, sa.self_attn.out_proj.weight, sa.self_attn.out_proj.bias))
+            ff = self.transformer_ffn_layers[i]
+            output = ff.norm(output + ff.linear2(torch.relu(ff.linear1(output))))
+            dec = heads(output)
+        Q = output.shape[0]
+        if mask_features.requires_grad and torch.is_grad_enabled():
+            masks = [Fn.mask_logits(e.contiguous(), mask_features) for e in embs]
+        else:
+            masks = list(Fn.mask_logits(torch.cat(embs, dim=1), feats).split(Q, dim=1))
+        return output, dec, logits, masks
+
+    def _train_inputs(self, x, mask_features):
+        """The maps in the parameters' dtype: fp32; a module moved to double (tests: the fp64 yardstick) stays there."""
+        assert len(x) == self.num_feature_levels
+        dt = self.decoder_norm.weight.dtype
+        return [m.to(dt) for m in x], mask_features.to(dt).contiguous()
+
+    @staticmethod
+    def _train_video_outputs(b, t, logits, masks):
+        """'(b t) q c -> b t q c' and '(b t) q h w -> b q t h w' of all L + 1 predictions; the first L are the aux_outputs."""
+        logits = [z.unflatten(0, (b, t)) for z in logits]
+        masks = [z.unflatten(0, (b, t)).transpose(1, 2) for z in masks]
+        return {"pred_logits": logits[-1], "pred_masks": masks[-1],
+                "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(logits[:-1], masks[:-1])]}
+
+    def _train_clips(self, N):
+        """(b, t) of the (b t) frames of a training batch (…decoder.py:327-329)."""
+        t = self.num_frames
+        if t < 1 or N % t:
+            raise ValueError(f"{type(self).__name__}: a training batch holds (b t) frames with t = num_frames = {t}; got {N} frames")
+        return N // t, t
+
 
 @TRANSFORMER_DECODER_REGISTRY.register()
 class MultiScaleMaskedTransformerDecoder(_MaskedDecoderBase):
-    """Image Mask2Former decoder (BASELINE config #1).  Inference outputs only (no aux_outputs)."""
+    """Image Mask2Former decoder (BASELINE config #1).  aux_outputs: the first L of the L + 1 predictions under .train(), [] in eval."""
 
     @classmethod
     def from_config(cls, cfg, in_channels, mask_classification):
@@ -302,6 +400,11 @@ class MultiScaleMaskedTransformerDecoder(_MaskedDecoderBase):
     @Fn.fp32_island
     def forward(self, x, mask_features, mask=None):
         assert len(x) == self.num_feature_levels
+        if self.training:
+            x, mask_features = self._train_inputs(x, mask_features)
+            _, _, logits, masks = self._train_layers(x, mask_features)
+            return {"pred_logits": logits[-1], "pred_masks": masks[-1],
+                    "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(logits[:-1], masks[:-1])]}
         x, mask_features = self._f32_inputs(x, mask_features)
         output = self._run_layers(x, mask_features)
         _, logits, masks = self._final_heads(output, mask_features, True)
@@ -341,7 +444,7 @@ class VideoMultiScaleMaskedTransformerDecoder_dvisPlus(_MaskedDecoderBase):
         pred_reid_embed (1,C,T,Q), mask_features (T,Cm,H,W)."""
         assert len(x) == self.num_feature_levels
         if self.training:
-            raise NotImplementedError("dvis_plus_amd decoders implement the inference path")
+            return self._forward_train(x, mask_features)
         x, mask_features = self._f32_inputs(x, mask_features)
         output = self._run_layers(x, mask_features)
         dec, logits, masks = self._final_heads(output, mask_features, self.compute_pred_masks)
@@ -357,6 +460,22 @@ class VideoMultiScaleMaskedTransformerDecoder_dvisPlus(_MaskedDecoderBase):
             "pred_reid_embed": reid_b,
             "mask_features": mask_features,
         }
+
+
+    def _forward_train(self, x, mask_features):
+        """Training semantics of the reference (…decoder.py:326-354): the (b t) frames are b clips of num_frames; pred_logits
+        (b,t,Q,K+1), pred_masks (b,Q,t,H,W) — always computed, compute_pred_masks is an inference switch —, aux_outputs for the
+        learnable queries and the first L - 1 layers, embeddings (b,·,t,Q) composed as in eval."""
+        x, mask_features = self._train_inputs(x, mask_features)
+        b, t = self._train_clips(x[0].shape[0])
+        output, dec, logits, masks = self._train_layers(x, mask_features)
+        out = self._train_video_outputs(b, t, logits, masks)
+        to_bctq = lambda z: z.unflatten(0, (b, t)).permute(0, 3, 1, 2)                           # ((b t),Q,C) -> (b,C,t,Q)
+        reid_b = to_bctq(self._train_mlp(self.reid_embed, dec))
+        out.update(pred_embds=torch.cat([to_bctq(dec), reid_b], dim=1),
+                   pred_embds_without_norm=torch.cat([to_bctq(output.transpose(0, 1)), reid_b], dim=1),
+                   pred_reid_embed=reid_b, mask_features=mask_features)
+        return out
 
 
 @TRANSFORMER_DECODER_REGISTRY.register()
@@ -381,7 +500,14 @@ class VideoMultiScaleMaskedTransformerDecoder_dvis(_MaskedDecoderBase):
     @Fn.fp32_island
     def forward(self, x, mask_features, mask=None):
         if self.training:
-            raise NotImplementedError("dvis_plus_amd decoders implement the inference path")
+            x, mask_features = self._train_inputs(x, mask_features)
+            b, t = self._train_clips(x[0].shape[0])
+            output, dec, logits, masks = self._train_layers(x, mask_features)
+            out = self._train_video_outputs(b, t, logits, masks)
+            to_bctq = lambda z: z.unflatten(0, (b, t)).permute(0, 3, 1, 2)                       # ((b t),Q,C) -> (b,C,t,Q)
+            out.update(pred_embds=to_bctq(dec), pred_embds_without_norm=to_bctq(output.transpose(0, 1)),
+                       mask_features=mask_features)
+            return out
         x, mask_features = self._f32_inputs(x, mask_features)
         output = self._run_layers(x, mask_features)
         dec, logits, masks = self._final_heads(output, mask_features, True)

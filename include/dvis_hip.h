@@ -25,7 +25,9 @@
  *                               ReferringCrossAttentionLayer (dvis_Plus/tracker.py:8-92), TemporalRefiner (dvis_Plus/refiner.py:104-139)
  *   dvis_attention_backward  <- autograd's backward of that core without a mask (training of the temporal refiner,
  *                               dvis_Plus/refiner.py:104-139)
- *   dvis_add_layernorm       <- `norm(tgt + tgt2)` of every post-norm residual block (msdeformattn.py:125-131,
+ *   dvis_masked_attention_backward <- the same with a mask and up to 65 536 keys (training of the masked-attention decoder's
+ *                               cross-attention, dvis_Plus/video_mask2former_transformer_decoder.py:294-303)
+ *   dvis_add_layernorm      <- `norm(tgt + tgt2)` of every post-norm residual block (msdeformattn.py:125-131,
  *                               video_mask2former_transformer_decoder.py:47-50,108-111,166-170, tracker.py:51-53)
  *   dvis_nchw_to_tokens      <- src.flatten(2).transpose(1, 2) + torch.cat over levels, msdeformattn.py:64-79
  *   dvis_bias_act            <- FrozenBN shift + shortcut add + ReLU after each backbone convolution (detectron2 BottleneckBlock)
@@ -308,6 +310,37 @@ int dvis_attention_backward(const float *q, const int64_t *q_strides, const floa
 /* Threads per workgroup of that launch: 64, 128 or 256 (one per key; the row reductions then run over 4, 8 or 16 lanes per query row);
  * 0 for an Lk the kernel does not serve.  Host only; the launch takes its block size from it. */
 int dvis_attention_backward_threads(int Lk);
+
+/*
+ * Backward of softmax(Q K^T * scale [+ mask]) V for long key sequences with the forward's mask semantics (training of the
+ * segmenter's masked-attention decoder: 100 - 200 queries over every pixel of a feature level), fp32, exact fp32 FMA arithmetic,
+ * deterministic (no float atomics):
+ *   P = softmax over the allowed keys   dV = P^T dO   dP = dO V^T   D = rowsum(P o dP)   dS = P o (dP - D)
+ *   dQ = scale * dS K                   dK = scale * dS^T Q
+ * P is recomputed from q and k, and D from that P: nothing of the forward is needed.
+ *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward (x_strides[3] =
+ *   {batch, head, row} in floats, d contiguous, 16-byte aligned, strides multiples of 4 floats); d in {32, 64};
+ *   1 <= Lq <= 256, 1 <= Lk <= 65536.
+ *   mask: NULL or uint8 (B, Lq, Lk), 1 = blocked, shared by the heads (rows need no alignment); a blocked key has P = 0 exactly.
+ *   allowed_count: int32 (B, Lq), required beside a mask; a row with count 0 ignores its mask.
+ *   dq (Lq, B, heads * d), dk / dv (Lk, B, heads * d): contiguous outputs.
+ *   ws: dvis_masked_attention_backward_ws_bytes(B * heads, Lq, Lk, d) bytes, 16-byte aligned (row statistics, per-key-tile
+ *   (max, sum, sum of 2^x dP) triples and per-key-tile shares of dQ; 0 for sizes the kernel does not serve).
+ * The keys are cut into tiles of `key_tile` over workgroups; four launches (tile statistics, row statistics, dK / dV and the tiles'
+ * shares of dQ, dQ).  Every sum has one order that depends on (Lq, Lk, d) alone, so the bits of a (batch entry, head) do not depend
+ * on B.
+ */
+int64_t dvis_masked_attention_backward_ws_bytes(int BH, int Lq, int Lk, int d);
+int dvis_masked_attention_backward(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
+                                   const float *v, const int64_t *v_strides,
+                                   const float *grad_out, const int64_t *g_strides, const uint8_t *mask,
+                                   const int32_t *allowed_count, float *dq, float *dk, float *dv, int B, int heads, int Lq,
+                                   int Lk, int d, float scale, void *ws, void *stream);
+/* How that launch cuts the work — host only; the launch takes its grid, block and LDS size from the same function.
+ *   plan[5] = {key_tile, query_tile, n_key_tiles, threads, lds_bytes}: keys per workgroup, queries per chunk inside a workgroup,
+ *   workgroups per (batch entry, head), threads per workgroup (one per key of the tile), dynamic LDS of the two tile launches.
+ * Refuses the sizes the launch refuses. */
+int dvis_masked_attention_backward_plan(int Lq, int Lk, int d, int32_t *plan);
 
 /*
  * out[r, :] = LayerNorm(x[r, :] + res[r, :]) * gamma + beta, rows x C fp32 (C % 4 == 0, C <= 1024); `res` may be NULL
