@@ -24,23 +24,15 @@
 
 #include <type_traits>
 
-#include "dvis_common.h"
+#include "attention_common.h"
 #include "x3_common.h"
 
 namespace {
 
-// The softmax runs in base 2: q is pre-scaled by scale * log2(e), so exp(s - m) is ONE v_exp_f32 (a quarter-rate
-// transcendental) per score instead of expf's range reduction around it — the VALU work per 16 x 16 score tile was
-// 154 instructions against 16 MFMAs (PMC, decoder cross-attention), i.e. as many issue cycles as the matrix work.
-// Row statistics (m, and the combine kernel's weights) live in the same base-2 units; the normalised output does not care.
-constexpr float kLog2e = 1.4426950408889634f;
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
+// The softmax runs in base 2 (kLog2e, ex2 of attention_common.h): q is pre-scaled by scale * log2(e).  With expf the VALU work per
+// 16 x 16 score tile was 154 instructions against 16 MFMAs (PMC, decoder cross-attention), i.e. as many issue cycles as the matrix
+// work.  The combine kernel's weights live in the same base-2 units.
 constexpr int kKT = 64;   // keys per LDS stage
-
-struct dvis_strides {
-  int64_t b, h, r;   // floats between batch entries / heads / rows (last dim contiguous)
-};
 
 struct SplitPlan {
   int nsplit, keys_per_split, qchunks;
@@ -1108,15 +1100,12 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
                             float scale, void *ws, void *stream, int kernel) {
   DVIS_REQUIRE(B >= 0 && heads > 0 && Lq >= 0 && Lk > 0, "attention: bad sizes");
   if (B == 0 || Lq == 0) return DVIS_OK;
-  DVIS_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && o_strides, "attention: null pointer");
+  if (const int rc = attn_check_views("attention", "q/k/v", {q, k, v}, {q_strides, k_strides, v_strides}, {out, o_strides})) return rc;
   const int BH = B * heads;
   AttnPlan plan;
   if (const int rc = attention_decide(BH, Lq, Lk, d, mask != nullptr, k_strides[2], v_strides[2], kernel, &plan)) return rc;
-  const dvis_strides qs{q_strides[0], q_strides[1], q_strides[2]}, ks{k_strides[0], k_strides[1], k_strides[2]};
-  const dvis_strides vs{v_strides[0], v_strides[1], v_strides[2]}, os{o_strides[0], o_strides[1], o_strides[2]};
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v;
-  DVIS_REQUIRE((al & 15) == 0 && ((qs.b | qs.h | qs.r | ks.b | ks.h | ks.r | vs.b | vs.h | vs.r) & 3) == 0,
-               "attention: q/k/v must be 16-byte aligned with strides that are multiples of 4 floats");
+  const dvis_strides qs = dvis_strides_from(q_strides), ks = dvis_strides_from(k_strides);
+  const dvis_strides vs = dvis_strides_from(v_strides), os = dvis_strides_from(o_strides);
   DVIS_REQUIRE(mask == nullptr || ((uintptr_t)mask & 3) == 0, "attention: mask must be 4-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   if (plan.served_by == DVIS_ATTN_X3) {
@@ -1196,7 +1185,7 @@ DVIS_EXPORT int dvis_attention_x3_packed(const void *ws, float *out, const int64
   DVIS_REQUIRE((uintptr_t)ws % 16 == 0, "attention_x3_packed: workspace must be 16-byte aligned");
   if (B == 0) return DVIS_OK;
   const int BH = B * heads;
-  const dvis_strides os{o_strides[0], o_strides[1], o_strides[2]};
+  const dvis_strides os = dvis_strides_from(o_strides);
   const X3Guard gd = dvis_x3_guard();
   hipLaunchKernelGGL(attn_x3_kernel<false>, dim3(((BH + 7) / 8) * 8 * ((L + 127) / 128)), dim3(512), 0, (hipStream_t)stream, (const _Float16 *)ws, out,
                      os, BH, heads, L, L, gd.flag, gd.tag);

@@ -24,20 +24,11 @@
 //     by scale * log2(e)).
 #include <math.h>
 
-#include "dvis_common.h"
+#include "attention_common.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kQC = 16;        // queries per chunk
 constexpr int kMaxLk = 256;    // one thread per key
-constexpr size_t kLdsLimit = 160 * 1024;
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-struct dvis_strides {
-  int64_t b, h, r;   // floats between batch entries / heads / rows (last dim contiguous)
-};
 
 __host__ __device__ inline int score_stride(int Lk) { return Lk | 1; }
 
@@ -85,6 +76,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
 
   for (int q0 = 0; q0 < Lq; q0 += kQC) {
     // ---- (1) the chunk's rows of Q and dO; rows past Lq are zeros (they then add exact zeros to dK and dV)
+    // (the text of bwd_load_chunk, inline: through the helper hipcc issues both global loads after both address computations, and
+    // the d = 64 kernel measured 0.3 - 0.5 us of 275 slower at Lq 100, Lk 256)
     for (int e = tid; e < kQC * C4; e += nthr) {
       const int row = e / C4, c4 = e - row * C4;
       float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
@@ -97,31 +90,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     }
     __syncthreads();
 
-    // ---- (2) this key's column: s = q_i . k_t (log2 units), dp = dO_i . v_t.  Each dot product runs as FOUR fma chains, one per
-    // component of the float4 pieces (dims c, c + 4, c + 8, ...), summed pairwise at the end: a single chain over d = 64 unscaled
-    // products carried 4 - 8 times the rounding error of a blocked fp32 dot product into the scores (with one query nothing
-    // averages it out of dv = p dO: 4.8e-07 against 1.1e-07 of an fp32 CPU run at Lq 1, Lk 17, d 64), and four independent
-    // chains are four times shorter on the fma latency.  (The loop over the rows stays rolled: unrolled, hipcc issues the LDS
-    // reads of all 16 rows first and spills a thousand registers.)
+    // ---- (2) this key's column: s = q_i . k_t (log2 units), dp = dO_i . v_t (bwd_dots says how, and why the loop stays rolled)
 #pragma unroll 1
     for (int i = 0; key_on && i < kQC; ++i) {
-      float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = s4;
-#pragma unroll
-      for (int c = 0; c < C4; ++c) {
-        const float4 kk = *reinterpret_cast<const float4 *>(krow + 4 * c);
-        const float4 vv = vr[c];
-        const float4 qq = *reinterpret_cast<const float4 *>(&q_lds[i * LS + 4 * c]);
-        const float4 gg = *reinterpret_cast<const float4 *>(&g_lds[i * LS + 4 * c]);
-        s4.x = fmaf(qq.x, kk.x, s4.x);
-        s4.y = fmaf(qq.y, kk.y, s4.y);
-        s4.z = fmaf(qq.z, kk.z, s4.z);
-        s4.w = fmaf(qq.w, kk.w, s4.w);
-        d4.x = fmaf(gg.x, vv.x, d4.x);
-        d4.y = fmaf(gg.y, vv.y, d4.y);
-        d4.z = fmaf(gg.z, vv.z, d4.z);
-        d4.w = fmaf(gg.w, vv.w, d4.w);
-      }
-      const float s = (s4.x + s4.y) + (s4.z + s4.w), dp = (d4.x + d4.y) + (d4.z + d4.w);
+      float s, dp;
+      bwd_dots<DH>(krow, vr, &q_lds[i * LS], &g_lds[i * LS], &s, &dp);
       s_lds[i * SS + tid] = s * sl2;
       p_lds[i * SS + tid] = dp;
     }
@@ -161,19 +134,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
       const float p = ex2(s_lds[at] - st_lds[i * 4]) * st_lds[i * 4 + 1];
       const float ds = p * (p_lds[at] - st_lds[i * 4 + 2]);
       s_lds[at] = ds;
-#pragma unroll
-      for (int c = 0; c < C4; ++c) {
-        const float4 qq = *reinterpret_cast<const float4 *>(&q_lds[i * LS + 4 * c]);
-        const float4 gg = *reinterpret_cast<const float4 *>(&g_lds[i * LS + 4 * c]);
-        dva[c].x = fmaf(p, gg.x, dva[c].x);
-        dva[c].y = fmaf(p, gg.y, dva[c].y);
-        dva[c].z = fmaf(p, gg.z, dva[c].z);
-        dva[c].w = fmaf(p, gg.w, dva[c].w);
-        dka[c].x = fmaf(ds, qq.x, dka[c].x);
-        dka[c].y = fmaf(ds, qq.y, dka[c].y);
-        dka[c].z = fmaf(ds, qq.z, dka[c].z);
-        dka[c].w = fmaf(ds, qq.w, dka[c].w);
-      }
+      bwd_accumulate<DH>(p, ds, &q_lds[i * LS], &g_lds[i * LS], dka, dva);
     }
     __syncthreads();
 
@@ -194,11 +155,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   if (key_on) {
     float *dkrow = dk + ((size_t)tid * B + bi) * C + hi * DH;
     float *dvrow = dv + ((size_t)tid * B + bi) * C + hi * DH;
-#pragma unroll
-    for (int c = 0; c < C4; ++c) {
-      *reinterpret_cast<float4 *>(dkrow + 4 * c) = make_float4(dka[c].x * scale, dka[c].y * scale, dka[c].z * scale, dka[c].w * scale);
-      *reinterpret_cast<float4 *>(dvrow + 4 * c) = dva[c];
-    }
+    bwd_store_dkdv<DH>(dkrow, dvrow, dka, dva, scale);
   }
 }
 
@@ -219,14 +176,12 @@ DVIS_EXPORT int dvis_attention_backward(const float *q, const int64_t *q_strides
   DVIS_REQUIRE(d == 32 || d == 64, "attention_backward: head dim must be 32 or 64 (got %d)", d);
   DVIS_REQUIRE(Lk <= kMaxLk, "attention_backward: serves at most %d keys (got Lk=%d)", kMaxLk, Lk);
   if (B == 0) return DVIS_OK;
-  DVIS_REQUIRE(q && k && v && grad_out && dq && dk && dv && q_strides && k_strides && v_strides && g_strides,
-               "attention_backward: null pointer");
+  if (const int rc = attn_check_views("attention_backward", "q/k/v/grad_out", {q, k, v, grad_out, dq, dk, dv},
+                                      {q_strides, k_strides, v_strides, g_strides}))
+    return rc;
   DVIS_REQUIRE((long long)B * heads < (1ll << 31), "attention_backward: batch*heads must be below 2^31");
-  const dvis_strides qs{q_strides[0], q_strides[1], q_strides[2]}, ks{k_strides[0], k_strides[1], k_strides[2]};
-  const dvis_strides vs{v_strides[0], v_strides[1], v_strides[2]}, gs{g_strides[0], g_strides[1], g_strides[2]};
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)grad_out | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv;
-  DVIS_REQUIRE((al & 15) == 0 && ((qs.b | qs.h | qs.r | ks.b | ks.h | ks.r | vs.b | vs.h | vs.r | gs.b | gs.h | gs.r) & 3) == 0,
-               "attention_backward: q/k/v/grad_out must be 16-byte aligned with strides that are multiples of 4 floats");
+  const dvis_strides qs = dvis_strides_from(q_strides), ks = dvis_strides_from(k_strides);
+  const dvis_strides vs = dvis_strides_from(v_strides), gs = dvis_strides_from(g_strides);
   const size_t lds = lds_floats(Lk, d) * sizeof(float);
   DVIS_REQUIRE(lds <= kLdsLimit, "attention_backward: %zu bytes of LDS exceed the %zu of a workgroup", lds, kLdsLimit);
   static DvisLdsOptIn opted32, opted64;

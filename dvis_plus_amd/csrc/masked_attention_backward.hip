@@ -30,23 +30,14 @@
 // partials cost Lq * d floats per tile written and read once.
 #include <math.h>
 
-#include "dvis_common.h"
+#include "attention_common.h"
 
 namespace {
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr int kQC = 16;        // queries per chunk
 constexpr int kKT = 256;       // keys per tile = threads per workgroup: one thread per key
 constexpr int kMaxLq = 256;
 constexpr int kMaxLk = 65536;
 constexpr int kSS = kKT + 1;   // row stride of the chunk's dS in LDS
-constexpr size_t kLdsLimit = 160 * 1024;
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-struct dvis_strides {
-  int64_t b, h, r;   // floats between batch entries / heads / rows (last dim contiguous)
-};
 
 struct mab_plan {
   int key_tile, query_tile, n_key_tiles, threads, k_rows;
@@ -133,16 +124,7 @@ __global__ __launch_bounds__(kKT) void mab_tile_kernel(
     }
     // ---- (1) the chunk's rows of Q and dO; rows past Lq are zeros.  PASS 1: the rows' statistics; a row past Lq gets 1 / l = 0,
     // so its P and dS are exact zeros
-    for (int e = tid; e < kQC * C4; e += kKT) {
-      const int row = e / C4, c4 = e - row * C4;
-      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-      if (q0 + row < Lq) {
-        a = *reinterpret_cast<const float4 *>(qb + (size_t)(q0 + row) * qs.r + 4 * c4);
-        b = *reinterpret_cast<const float4 *>(gb + (size_t)(q0 + row) * gs.r + 4 * c4);
-      }
-      *reinterpret_cast<float4 *>(&q_lds[row * LS + 4 * c4]) = a;
-      *reinterpret_cast<float4 *>(&g_lds[row * LS + 4 * c4]) = b;
-    }
+    bwd_load_chunk<DH>(q_lds, g_lds, qb, gb, qs.r, gs.r, q0, Lq, tid, kKT);
     if (tid < kQC) {
       const int row = q0 + tid;
       float m = 0.f, inv = 0.f, D = 0.f, masked = 0.f;
@@ -162,34 +144,20 @@ __global__ __launch_bounds__(kKT) void mab_tile_kernel(
     }
     __syncthreads();
 
-    // ---- (2) this key's column.  Each dot product over d runs as FOUR fma chains, one per component of the float4 pieces, summed
-    // pairwise (attention_backward.hip says why).  The loop over the rows stays rolled.
+    // ---- (2) this key's column: s = q_i . k_t (log2 units), dp = dO_i . v_t (bwd_dots says how, and why the loop stays rolled)
 #pragma unroll 1
     for (int i = 0; i < kQC; ++i) {
       float s = 0.f, dp = 0.f;
       bool open = false;
       if (key_on) {
-        float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f), d4 = s4;
-#pragma unroll
-        for (int c = 0; c < C4; ++c) {
-          float4 kk;
-          if constexpr (kRegs) kk = kr[c];
-          else kk = *reinterpret_cast<const float4 *>(krow + 4 * c);
-          const float4 qq = *reinterpret_cast<const float4 *>(&q_lds[i * LS + 4 * c]);
-          s4.x = fmaf(qq.x, kk.x, s4.x);
-          s4.y = fmaf(qq.y, kk.y, s4.y);
-          s4.z = fmaf(qq.z, kk.z, s4.z);
-          s4.w = fmaf(qq.w, kk.w, s4.w);
-          const float4 vv = vr[c];
-          const float4 gg = *reinterpret_cast<const float4 *>(&g_lds[i * LS + 4 * c]);
-          d4.x = fmaf(gg.x, vv.x, d4.x);
-          d4.y = fmaf(gg.y, vv.y, d4.y);
-          d4.z = fmaf(gg.z, vv.z, d4.z);
-          d4.w = fmaf(gg.w, vv.w, d4.w);
-        }
+        // (results in locals of this block: handing bwd_dots the addresses of s and dp, which live across the branch, cost 40 - 130
+        // registers per thread)
+        float s_raw, dp_raw;
+        if constexpr (kRegs) bwd_dots<DH>(&kr[0], vr, &q_lds[i * LS], &g_lds[i * LS], &s_raw, &dp_raw);
+        else bwd_dots<DH>(krow, vr, &q_lds[i * LS], &g_lds[i * LS], &s_raw, &dp_raw);
         // (__fmul_rn: never contracted with the subtraction of the row maximum — both passes must hold the same bits)
-        s = __fmul_rn((s4.x + s4.y) + (s4.z + s4.w), sl2);
-        dp = (d4.x + d4.y) + (d4.z + d4.w);
+        s = __fmul_rn(s_raw, sl2);
+        dp = dp_raw;
         open = true;
         if (st_lds[i * 4 + 3] != 0.f) open = ((blocked >> i) & 1u) == 0;
       }
@@ -202,19 +170,7 @@ __global__ __launch_bounds__(kKT) void mab_tile_kernel(
         const float p = open ? ex2(s - st_lds[i * 4]) * st_lds[i * 4 + 1] : 0.f;
         const float ds = open ? p * (dp - st_lds[i * 4 + 2]) : 0.f;
         s_lds[i * kSS + tid] = ds;
-#pragma unroll
-        for (int c = 0; c < C4; ++c) {
-          const float4 qq = *reinterpret_cast<const float4 *>(&q_lds[i * LS + 4 * c]);
-          const float4 gg = *reinterpret_cast<const float4 *>(&g_lds[i * LS + 4 * c]);
-          dva[c].x = fmaf(p, gg.x, dva[c].x);
-          dva[c].y = fmaf(p, gg.y, dva[c].y);
-          dva[c].z = fmaf(p, gg.z, dva[c].z);
-          dva[c].w = fmaf(p, gg.w, dva[c].w);
-          dka[c].x = fmaf(ds, qq.x, dka[c].x);
-          dka[c].y = fmaf(ds, qq.y, dka[c].y);
-          dka[c].z = fmaf(ds, qq.z, dka[c].z);
-          dka[c].w = fmaf(ds, qq.w, dka[c].w);
-        }
+        bwd_accumulate<DH>(p, ds, &q_lds[i * LS], &g_lds[i * LS], dka, dva);
       }
     }
     __syncthreads();
@@ -271,14 +227,9 @@ __global__ __launch_bounds__(kKT) void mab_tile_kernel(
     // stands between these reads of s_lds / p_lds / o_lds and the next step (2))
   }
 
-  if constexpr (PASS != 0) if (key_on) {
-    float *dkrow = dk + ((size_t)key * B + bi) * C + hi * DH;
-    float *dvrow = dv + ((size_t)key * B + bi) * C + hi * DH;
-#pragma unroll
-    for (int c = 0; c < C4; ++c) {
-      *reinterpret_cast<float4 *>(dkrow + 4 * c) = make_float4(dka[c].x * scale, dka[c].y * scale, dka[c].z * scale, dka[c].w * scale);
-      *reinterpret_cast<float4 *>(dvrow + 4 * c) = dva[c];
-    }
+  if constexpr (PASS != 0) {
+    const size_t at = ((size_t)key * B + bi) * C + hi * DH;
+    if (key_on) bwd_store_dkdv<DH>(dk + at, dv + at, dka, dva, scale);
   }
 }
 
@@ -343,8 +294,9 @@ int check_sizes(const char *who, int Lq, int Lk, int d) {
 }
 
 template <int DH>
-int launch(const float *q, dvis_strides qs, const float *k, dvis_strides ks, const float *v, dvis_strides vs, const float *go, dvis_strides gs, const uint8_t *mask, const int32_t *allowed, float *dq, float *dk,
-           float *dv, int B, int heads, int Lq, int Lk, float scale, float *ws, const mab_plan &plan, hipStream_t st) {
+int launch(const float *q, dvis_strides qs, const float *k, dvis_strides ks, const float *v, dvis_strides vs, const float *go,
+           dvis_strides gs, const uint8_t *mask, const int32_t *allowed, float *dq, float *dk, float *dv, int B, int heads, int Lq,
+           int Lk, float scale, float *ws, const mab_plan &plan, hipStream_t st) {
   const size_t BH = (size_t)B * heads;
   const int nkt = plan.n_key_tiles;
   float *stats = ws, *pstats = stats + ws_stats(BH, Lq), *part = pstats + ws_pstats(BH, Lq, nkt);
@@ -398,18 +350,15 @@ DVIS_EXPORT int dvis_masked_attention_backward(const float *q, const int64_t *q_
   DVIS_REQUIRE(B >= 0 && heads > 0, "masked_attention_backward: bad sizes");
   if (const int rc = check_sizes("masked_attention_backward", Lq, Lk, d)) return rc;
   if (B == 0) return DVIS_OK;
-  DVIS_REQUIRE(q && k && v && grad_out && dq && dk && dv && ws && q_strides && k_strides && v_strides && g_strides,
-               "masked_attention_backward: null pointer");
+  if (const int rc = attn_check_views("masked_attention_backward", "q/k/v/grad_out", {q, k, v, grad_out, dq, dk, dv, ws},
+                                      {q_strides, k_strides, v_strides, g_strides}))
+    return rc;
   DVIS_REQUIRE(mask == nullptr || allowed_count != nullptr, "masked_attention_backward: a mask needs its allowed_count");
   const mab_plan plan = make_plan(Lk, d);
   DVIS_REQUIRE((long long)B * heads * plan.n_key_tiles < (1ll << 31),
                "masked_attention_backward: batch*heads*key tiles must be below 2^31");
-  const dvis_strides qs{q_strides[0], q_strides[1], q_strides[2]}, ks{k_strides[0], k_strides[1], k_strides[2]};
-  const dvis_strides vs{v_strides[0], v_strides[1], v_strides[2]}, gs{g_strides[0], g_strides[1], g_strides[2]};
-  const uintptr_t al = (uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)grad_out | (uintptr_t)dq |
-                       (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)ws;
-  DVIS_REQUIRE((al & 15) == 0 && ((qs.b | qs.h | qs.r | ks.b | ks.h | ks.r | vs.b | vs.h | vs.r | gs.b | gs.h | gs.r) & 3) == 0,
-               "masked_attention_backward: q/k/v/grad_out must be 16-byte aligned with strides that are multiples of 4 floats");
+  const dvis_strides qs = dvis_strides_from(q_strides), ks = dvis_strides_from(k_strides);
+  const dvis_strides vs = dvis_strides_from(v_strides), gs = dvis_strides_from(g_strides);
   DVIS_REQUIRE(plan.lds_bytes <= kLdsLimit, "masked_attention_backward: %zu bytes of LDS exceed the %zu of a workgroup",
                plan.lds_bytes, kLdsLimit);
   hipStream_t st = (hipStream_t)stream;

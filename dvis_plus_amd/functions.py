@@ -507,7 +507,7 @@ def attention(q, k, v, nheads, mask=None, allowed_count=None, out=None, short=Fa
             raise RuntimeError("attention: out= cannot be combined with an input that requires grad (the result must be a new "
                                "tensor of the autograd graph)")
         _attention_backward_check(q, k, v, None, nheads)
-        return AttentionFunction.apply(q, k, v, nheads, short)
+        return AttentionFunction.apply(q, k, v, nheads, None, None, short, False)
     return _attention_kernel(q, k, v, nheads, mask, allowed_count, out, short)
 
 
@@ -582,122 +582,47 @@ def _attention_kernel(q, k, v, nheads, mask=None, allowed_count=None, out=None, 
 
 
 ATTENTION_BACKWARD_MAX_KEYS = 256
-
-
-def _attention_backward_check(q, k, v, grad_out, nheads):
-    """The contract of csrc/attention_backward.hip, checked on the host before anything is launched."""
-    tensors = [("q", q), ("k", k), ("v", v)] + ([("grad_out", grad_out)] if grad_out is not None else [])
-    for name, t in tensors:
-        if not t.is_cuda or t.dim() != 3:
-            raise RuntimeError(f"attention_backward: {name} must be a GPU (L, B, C) tensor")
-        if t.dtype != torch.float32:
-            raise RuntimeError(f"attention_backward: {name} must be float32 (got {t.dtype})")
-        if t.stride(2) != 1:
-            raise RuntimeError(f"attention_backward: {name} must have inner stride 1 (got {t.stride(2)})")
-    Lq, B, C = q.shape
-    Lk = k.shape[0]
-    if k.shape != v.shape or k.shape[1:] != q.shape[1:] or (grad_out is not None and grad_out.shape != q.shape):
-        raise RuntimeError("attention_backward: inconsistent q / k / v / grad_out shapes")
-    if C % nheads or C // nheads not in (32, 64):
-        raise RuntimeError(f"attention_backward: head dim must be 32 or 64 (got C={C} over {nheads} heads)")
-    if Lk > ATTENTION_BACKWARD_MAX_KEYS:
-        raise RuntimeError(f"attention_backward: serves at most {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
-    if Lq < 1 or Lk < 1:
-        raise RuntimeError(f"attention_backward: needs Lq >= 1 and Lk >= 1 (got Lq={Lq}, Lk={Lk})")
-
-
-def attention_backward(q, k, v, grad_out, nheads):
-    """Gradients of ``attention(q, k, v, nheads)`` (no mask) for the upstream gradient ``grad_out`` (csrc/attention_backward.hip):
-    q / grad_out (Lq, B, C), k / v (Lk, B, C) float32 GPU tensors with unit inner stride and arbitrary row / batch strides, head dim
-    32 or 64, Lk <= 256 -> (dq (Lq, B, C), dk (Lk, B, C), dv (Lk, B, C)), contiguous.  The probabilities are recomputed from q and
-    k.  Exact fp32, no atomics: the same bits on every call, and a batch entry's bits do not depend on B.  Anything outside the
-    contract raises before a launch; there is no torch formulation behind it for GPU tensors."""
-    _attention_backward_check(q, k, v, grad_out, nheads)
-    Lq, B, C = q.shape
-    Lk = k.shape[0]
-    d = C // nheads
-    dev = q.device
-    dq = torch.empty((Lq, B, C), dtype=torch.float32, device=dev)
-    dk = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
-    dv = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
-    if B == 0:
-        return dq, dk, dv
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = native.lib().dvis_attention_backward(
-            ptr(q), _strides3(q, B, C, d), ptr(k), _strides3(k, B, C, d), ptr(v), _strides3(v, B, C, d), ptr(grad_out),
-            _strides3(grad_out, B, C, d), ptr(dq), ptr(dk), ptr(dv), B, nheads, Lq, Lk, d, 1.0 / (d ** 0.5), native.stream_ptr(dev))
-    native.check(rc, "dvis_attention_backward")
-    return dq, dk, dv
-
-
-def attention_backward_threads(Lk):
-    """Threads per workgroup ``attention_backward`` launches for Lk keys (64, 128 or 256: 4, 8 or 16 lanes per query row in the row
-    reductions) — asked of the library, whose launch uses the same function."""
-    n = native.lib().dvis_attention_backward_threads(int(Lk))
-    if n <= 0:
-        raise RuntimeError(f"attention_backward: serves 1 .. {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
-    return n
-
-
-class AttentionFunction(Function):
-    """``attention`` (no mask) under autograd: the forward kernel as it is, csrc/attention_backward.hip for all three inputs."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, nheads, short):
-        ctx.save_for_backward(q, k, v)
-        ctx.nheads = nheads
-        return _attention_kernel(q, k, v, nheads, short=short)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out):
-        q, k, v = ctx.saved_tensors
-        # the kernel's view contract: unit inner stride, 16-byte aligned base, row / batch strides in multiples of 4 floats.  What
-        # autograd hands over need not meet it (the narrowed gradient of a concatenation, an odd stride on a dim of size 1): copy
-        B = grad_out.shape[1]
-        if grad_out.stride(2) != 1 or grad_out.data_ptr() % 16 or grad_out.stride(0) % 4 or (B > 1 and grad_out.stride(1) % 4):
-            grad_out = grad_out.contiguous()
-        dq, dk, dv = attention_backward(q, k, v, grad_out, ctx.nheads)
-        need = ctx.needs_input_grad
-        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None
-
-
 MASKED_ATTENTION_BACKWARD_MAX_QUERIES = 256
 MASKED_ATTENTION_BACKWARD_MAX_KEYS = 65536
 MaskedAttentionBackwardPlan = collections.namedtuple("MaskedAttentionBackwardPlan",
                                                      "key_tile query_tile n_key_tiles threads lds_bytes")
 
 
-def masked_attention_backward_plan(Lq, Lk, d):
-    """How ``masked_attention_backward`` cuts Lq queries and Lk keys of head dim d: MaskedAttentionBackwardPlan(key_tile, query_tile,
-    n_key_tiles, threads, lds_bytes) — keys per workgroup, queries per chunk inside it, workgroups per (batch entry, head), threads per
-    workgroup, dynamic LDS — asked of the library, whose launch uses the same function."""
-    plan = (ctypes.c_int32 * 5)()
-    native.check(native.lib().dvis_masked_attention_backward_plan(int(Lq), int(Lk), int(d), plan),
-                 "dvis_masked_attention_backward_plan")
-    return MaskedAttentionBackwardPlan(*plan)
-
-
-def _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_count, out=None):
-    """The contract of csrc/masked_attention_backward.hip, checked on the host before anything is launched.  Returns the mask as
-    uint8."""
+def _attention_grad_check(op, q, k, v, grad_out, nheads, out=None):
+    """What csrc/attention_backward.hip and csrc/masked_attention_backward.hip both ask of their tensors, checked on the host before
+    anything is launched; `op` names the caller in the messages."""
     tensors = [("q", q), ("k", k), ("v", v)] + [(n, t) for n, t in (("grad_out", grad_out), ("out", out)) if t is not None]
     for name, t in tensors:
         if not t.is_cuda or t.dim() != 3:
-            raise RuntimeError(f"masked_attention_backward: {name} must be a GPU (L, B, C) tensor")
+            raise RuntimeError(f"{op}: {name} must be a GPU (L, B, C) tensor")
         if t.dtype != torch.float32:
-            raise RuntimeError(f"masked_attention_backward: {name} must be float32 (got {t.dtype})")
+            raise RuntimeError(f"{op}: {name} must be float32 (got {t.dtype})")
         if t.stride(2) != 1:
-            raise RuntimeError(f"masked_attention_backward: {name} must have inner stride 1 (got {t.stride(2)})")
+            raise RuntimeError(f"{op}: {name} must have inner stride 1 (got {t.stride(2)})")
     Lq, B, C = q.shape
     Lk = k.shape[0]
     if k.shape != v.shape or k.shape[1:] != q.shape[1:] or any(t is not None and t.shape != q.shape for t in (grad_out, out)):
-        raise RuntimeError("masked_attention_backward: inconsistent q / k / v / grad_out / out shapes")
+        names = "q / k / v / grad_out" if op == "attention_backward" else "q / k / v / grad_out / out"      # (the first takes no out)
+        raise RuntimeError(f"{op}: inconsistent {names} shapes")
     if C % nheads or C // nheads not in (32, 64):
-        raise RuntimeError(f"masked_attention_backward: head dim must be 32 or 64 (got C={C} over {nheads} heads)")
+        raise RuntimeError(f"{op}: head dim must be 32 or 64 (got C={C} over {nheads} heads)")
     if Lq < 1 or Lk < 1:
-        raise RuntimeError(f"masked_attention_backward: needs Lq >= 1 and Lk >= 1 (got Lq={Lq}, Lk={Lk})")
+        raise RuntimeError(f"{op}: needs Lq >= 1 and Lk >= 1 (got Lq={Lq}, Lk={Lk})")
+
+
+def _attention_backward_check(q, k, v, grad_out, nheads):
+    """The contract of csrc/attention_backward.hip."""
+    _attention_grad_check("attention_backward", q, k, v, grad_out, nheads)
+    Lk = k.shape[0]
+    if Lk > ATTENTION_BACKWARD_MAX_KEYS:
+        raise RuntimeError(f"attention_backward: serves at most {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
+
+
+def _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_count, out=None):
+    """The contract of csrc/masked_attention_backward.hip.  Returns the mask as uint8."""
+    _attention_grad_check("masked_attention_backward", q, k, v, grad_out, nheads, out)
+    Lq, B, _ = q.shape
+    Lk = k.shape[0]
     if Lq > MASKED_ATTENTION_BACKWARD_MAX_QUERIES:
         raise RuntimeError(f"masked_attention_backward: serves at most {MASKED_ATTENTION_BACKWARD_MAX_QUERIES} queries (got Lq={Lq})")
     if Lk > MASKED_ATTENTION_BACKWARD_MAX_KEYS:
@@ -716,6 +641,60 @@ def _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_co
     return mask
 
 
+def _attention_grads_launch(q, k, v, grad_out, nheads, launch):
+    """What attention_backward and masked_attention_backward do alike: allocate dq (Lq, B, C), dk and dv (Lk, B, C) and, unless
+    B == 0, call ``launch(views, grads, sizes, dev)`` on q's device with the argument runs the library's two entry points share —
+    the (pointer, strides) pairs of q, k, v, grad_out; the pointers of dq, dk, dv; (B, heads, Lq, Lk, d, scale).  `launch` returns the
+    library's status and the entry point's name."""
+    Lq, B, C = q.shape
+    Lk = k.shape[0]
+    d = C // nheads
+    dev = q.device
+    dq = torch.empty((Lq, B, C), dtype=torch.float32, device=dev)
+    dk = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    dv = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
+    if B:
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        views = [a for t in (q, k, v, grad_out) for a in (ptr(t), _strides3(t, B, C, d))]
+        with torch.cuda.device(dev):
+            rc, what = launch(views, (ptr(dq), ptr(dk), ptr(dv)), (B, nheads, Lq, Lk, d, 1.0 / (d ** 0.5)), dev)
+        native.check(rc, what)
+    return dq, dk, dv
+
+
+def attention_backward(q, k, v, grad_out, nheads):
+    """Gradients of ``attention(q, k, v, nheads)`` (no mask) for the upstream gradient ``grad_out`` (csrc/attention_backward.hip):
+    q / grad_out (Lq, B, C), k / v (Lk, B, C) float32 GPU tensors with unit inner stride and arbitrary row / batch strides, head dim
+    32 or 64, Lk <= 256 -> (dq (Lq, B, C), dk (Lk, B, C), dv (Lk, B, C)), contiguous.  The probabilities are recomputed from q and
+    k.  Exact fp32, no atomics: the same bits on every call, and a batch entry's bits do not depend on B.  Anything outside the
+    contract raises before a launch; there is no torch formulation behind it for GPU tensors."""
+    _attention_backward_check(q, k, v, grad_out, nheads)
+
+    def launch(views, grads, sizes, dev):
+        return native.lib().dvis_attention_backward(*views, *grads, *sizes, native.stream_ptr(dev)), "dvis_attention_backward"
+
+    return _attention_grads_launch(q, k, v, grad_out, nheads, launch)
+
+
+def attention_backward_threads(Lk):
+    """Threads per workgroup ``attention_backward`` launches for Lk keys (64, 128 or 256: 4, 8 or 16 lanes per query row in the row
+    reductions) — asked of the library, whose launch uses the same function."""
+    n = native.lib().dvis_attention_backward_threads(int(Lk))
+    if n <= 0:
+        raise RuntimeError(f"attention_backward: serves 1 .. {ATTENTION_BACKWARD_MAX_KEYS} keys (got Lk={Lk})")
+    return n
+
+
+def masked_attention_backward_plan(Lq, Lk, d):
+    """How ``masked_attention_backward`` cuts Lq queries and Lk keys of head dim d: MaskedAttentionBackwardPlan(key_tile, query_tile,
+    n_key_tiles, threads, lds_bytes) — keys per workgroup, queries per chunk inside it, workgroups per (batch entry, head), threads per
+    workgroup, dynamic LDS — asked of the library, whose launch uses the same function."""
+    plan = (ctypes.c_int32 * 5)()
+    native.check(native.lib().dvis_masked_attention_backward_plan(int(Lq), int(Lk), int(d), plan),
+                 "dvis_masked_attention_backward_plan")
+    return MaskedAttentionBackwardPlan(*plan)
+
+
 def masked_attention_backward(q, k, v, grad_out, nheads, mask=None, allowed_count=None, out=None):
     """Gradients of ``masked_attention(q, k, v, nheads, mask, allowed_count)`` for the upstream gradient ``grad_out``
     (csrc/masked_attention_backward.hip): q / grad_out (Lq, B, C), k / v (Lk, B, C) float32 GPU tensors with unit inner stride and
@@ -727,62 +706,65 @@ def masked_attention_backward(q, k, v, grad_out, nheads, mask=None, allowed_coun
     the same bits on every call, and a batch entry's bits do not depend on B.  Anything outside the contract raises before a
     launch; there is no torch formulation behind it for GPU tensors."""
     mask = _masked_attention_backward_check(q, k, v, grad_out, nheads, mask, allowed_count, out)
-    Lq, B, C = q.shape
-    Lk = k.shape[0]
-    d = C // nheads
-    dev = q.device
-    dq = torch.empty((Lq, B, C), dtype=torch.float32, device=dev)
-    dk = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
-    dv = torch.empty((Lk, B, C), dtype=torch.float32, device=dev)
-    if B == 0:
-        return dq, dk, dv
-    lib = native.lib()
-    ws = torch.empty((lib.dvis_masked_attention_backward_ws_bytes(B * nheads, Lq, Lk, d) // 4,), dtype=torch.float32, device=dev)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        rc = lib.dvis_masked_attention_backward(
-            ptr(q), _strides3(q, B, C, d), ptr(k), _strides3(k, B, C, d), ptr(v), _strides3(v, B, C, d), ptr(grad_out),
-            _strides3(grad_out, B, C, d),
-            native.dev_ptr(mask, "mask") if mask is not None else None,
-            native.dev_ptr(allowed_count, "allowed_count") if mask is not None else None, ptr(dq), ptr(dk), ptr(dv), B, nheads, Lq, Lk,
-            d, 1.0 / (d ** 0.5), ptr(ws), native.stream_ptr(dev))
-    native.check(rc, "dvis_masked_attention_backward")
-    return dq, dk, dv
+
+    def launch(views, grads, sizes, dev):
+        lib = native.lib()
+        B, heads, Lq, Lk, d, _ = sizes
+        ws = torch.empty((lib.dvis_masked_attention_backward_ws_bytes(B * heads, Lq, Lk, d) // 4,), dtype=torch.float32, device=dev)
+        return lib.dvis_masked_attention_backward(
+            *views, native.dev_ptr(mask, "mask") if mask is not None else None,
+            native.dev_ptr(allowed_count, "allowed_count") if mask is not None else None, *grads, *sizes,
+            ctypes.c_void_p(ws.data_ptr()), native.stream_ptr(dev)), "dvis_masked_attention_backward"
+
+    return _attention_grads_launch(q, k, v, grad_out, nheads, launch)
 
 
-class MaskedAttentionFunction(Function):
-    """``masked_attention`` under autograd: the forward kernel as it is, csrc/masked_attention_backward.hip for q, k and v; the mask
-    and its counts get no gradient."""
+def _grad_out_for_kernel(grad_out):
+    """The backward kernels' view contract: unit inner stride, 16-byte aligned base, row / batch strides in multiples of 4 floats.
+    What autograd hands over need not meet it (the narrowed gradient of a concatenation, an odd stride on a dim of size 1): copy."""
+    B = grad_out.shape[1]
+    if grad_out.stride(2) != 1 or grad_out.data_ptr() % 16 or grad_out.stride(0) % 4 or (B > 1 and grad_out.stride(1) % 4):
+        return grad_out.contiguous()
+    return grad_out
+
+
+class AttentionFunction(Function):
+    """``attention`` (no mask) and ``masked_attention`` under autograd: the forward kernel as it is; for q, k and v
+    csrc/attention_backward.hip (tiled=False) or csrc/masked_attention_backward.hip (tiled=True: a mask, long key sequences).  Which
+    of the two is the caller's choice alone, never a function of Lk or of the mask; the mask and its counts get no gradient."""
 
     @staticmethod
-    def forward(ctx, q, k, v, nheads, mask, allowed_count):
+    def forward(ctx, q, k, v, nheads, mask, allowed_count, short, tiled):
         ctx.save_for_backward(q, k, v, mask, allowed_count)       # (not the output: the backward recomputes what it needs)
-        ctx.nheads = nheads
-        return _attention_kernel(q, k, v, nheads, mask, allowed_count)
+        ctx.nheads, ctx.tiled = nheads, tiled
+        return _attention_kernel(q, k, v, nheads, mask, allowed_count, short=short)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out):
         q, k, v, mask, allowed_count = ctx.saved_tensors
-        # the kernel's view contract (AttentionFunction.backward says what can miss it): copy
-        B = grad_out.shape[1]
-        if grad_out.stride(2) != 1 or grad_out.data_ptr() % 16 or grad_out.stride(0) % 4 or (B > 1 and grad_out.stride(1) % 4):
-            grad_out = grad_out.contiguous()
-        dq, dk, dv = masked_attention_backward(q, k, v, grad_out, ctx.nheads, mask, allowed_count)
+        grad_out = _grad_out_for_kernel(grad_out)
+        if ctx.tiled:
+            dq, dk, dv = masked_attention_backward(q, k, v, grad_out, ctx.nheads, mask, allowed_count)
+        else:
+            dq, dk, dv = attention_backward(q, k, v, grad_out, ctx.nheads)
         need = ctx.needs_input_grad
-        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None
+        return dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None, None, None
+
+
+MaskedAttentionFunction = AttentionFunction       # (the name DESIGN.md and CHANGELOG.md know masked_attention's wiring by)
 
 
 def masked_attention(q, k, v, nheads, mask=None, allowed_count=None):
     """``attention(q, k, v, nheads, mask, allowed_count)`` — the same forward kernel, the same bits — that is differentiable WITH a
-    mask and over long key sequences: an input that requires grad routes the call through MaskedAttentionFunction (backward
+    mask and over long key sequences: an input that requires grad routes the call through AttentionFunction (tiled=True: backward
     csrc/masked_attention_backward.hip: Lq <= 256, Lk <= 65536, head dim 32 or 64; a mask needs its allowed_count).  The
     cross-attention of the masked-attention decoder in training.  CPU tensors: cpu_ops.attention and torch's own autograd."""
     if _on_cpu(q, k, v):
         return cpu_ops.attention(q, k, v, nheads, mask, allowed_count)
     if torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad):
         mask = _masked_attention_backward_check(q, k, v, None, nheads, mask, allowed_count)
-        return MaskedAttentionFunction.apply(q, k, v, nheads, mask, allowed_count)
+        return AttentionFunction.apply(q, k, v, nheads, mask, allowed_count, False, True)
     return _attention_kernel(q, k, v, nheads, mask, allowed_count)
 
 

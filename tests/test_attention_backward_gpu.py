@@ -1,12 +1,9 @@
 """csrc/attention_backward.hip: the gradients of softmax(q k^T / sqrt(d)) v, their determinism, and the autograd wiring of
 functions.attention.
 
-Yardstick: fp64 autograd of the ``cpu_ops.attention`` composition on the CPU.  The bound of each of dq, dk, dv is measured, not
-chosen: 4 x the error of an fp32 CPU run against that fp64 run on the same inputs (4 = the project's factor for a different
-summation order, tests/test_mask_gemm_backward_gpu.py).  The kernel's exponential is the hardware's base-2 instruction where the
-CPU's is expf, so the fp32 CPU figure is the worse of two formulations per tensor: torch's softmax, and the same composition
-with torch.exp2 on scores scaled by scale * log2(e).  It is never the kernel's own output.  Every compared tensor has at least
-64 elements (test_tracker_train_gpu.cpu_baselines says why) except in the one-key case, which is exact.
+Yardstick: tests/attention_backward_cases.py — per tensor 4 x the error of the worse of two fp32 CPU formulations against fp64 autograd
+of the ``cpu_ops.attention`` composition on the same inputs, never the kernel's own output.  Every compared tensor has at least 64
+elements except in the one-key case, which is exact.
 
 With q = 0 every probability is exactly 1 / Lk; at Lk = 16 and integer v / grad_out every product and sum is exact in fp32, so dv
 must be bit-equal to the fp64 result and dk must be zero whatever the order: indexing and chunk-edge errors show without a
@@ -17,11 +14,10 @@ functions.attention_backward_threads) and the 16-query chunk edge at both head d
 tests/test_attention_edges_gpu.py: a target key per query that leads its row by >= 200 log2 units) makes dq and dk exactly zero and
 dv an exact integer sum; rows whose maxima run from -900 to +900 log2 units need the max subtraction in front of the exponential.
 Both assert their precondition on the CPU before the GPU is touched."""
-import math
-
 import pytest
 import torch
 
+from attention_backward_cases import check_against_fp64, cpu_grads, draw
 from test_attention_edges_gpu import assert_score_range, one_hot_inputs, one_hot_margin, score_range_inputs
 
 pytestmark = pytest.mark.gpu
@@ -44,50 +40,15 @@ def Fn():
 
 
 def _draw(Lq, Lk, B, heads, d, seed):
-    gen = torch.Generator().manual_seed(seed)
-    C = heads * d
-    return (torch.randn(Lq, B, C, generator=gen), torch.randn(Lk, B, C, generator=gen), torch.randn(Lk, B, C, generator=gen),
-            torch.randn(Lq, B, C, generator=gen))
-
-
-def _cpu_grads(q, k, v, go, heads, dtype, base2=False):
-    """(dq, dk, dv) by torch autograd of the cpu_ops.attention composition in `dtype`; base2: the softmax as exp2 on scores scaled
-    by scale * log2(e), normalised by their sum (what the kernel computes)."""
-    from dvis_plus_amd import cpu_ops
-    q, k, v = (t.to(dtype).clone().requires_grad_() for t in (q, k, v))
-    if not base2:
-        out = cpu_ops.attention(q, k, v, heads)
-    else:
-        Lq, B, C = q.shape
-        Lk, d = k.shape[0], C // heads
-        split = lambda t, n: t.reshape(n, B, heads, d).permute(1, 2, 0, 3)
-        s = (split(q, Lq) @ split(k, Lk).transpose(-1, -2)) * ((1.0 / d ** 0.5) * math.log2(math.e))
-        e = torch.exp2(s - s.amax(-1, keepdim=True))
-        out = ((e / e.sum(-1, keepdim=True)) @ split(v, Lk)).permute(2, 0, 1, 3).reshape(Lq, B, C)
-    return torch.autograd.grad(out, (q, k, v), go.to(dtype))
-
-
-def _bounds(q, k, v, go, heads):
-    ref = _cpu_grads(q, k, v, go, heads, torch.float64)
-    a = _cpu_grads(q, k, v, go, heads, torch.float32)
-    b = _cpu_grads(q, k, v, go, heads, torch.float32, base2=True)
-    base = [max((x.double() - r).abs().max().item(), (y.double() - r).abs().max().item()) for x, y, r in zip(a, b, ref)]
-    return ref, base
+    return draw(Lq, Lk, B, heads, d, seed, masked=False)[:4]
 
 
 @pytest.mark.parametrize("Lq,Lk,B,heads,d", SHAPES)
 def test_backward_against_fp64_and_determinism(Fn, Lq, Lk, B, heads, d):
     q, k, v, go = _draw(Lq, Lk, B, heads, d, 21)
-    ref, base = _bounds(q, k, v, go, heads)
-    dev = [t.cuda() for t in (q, k, v, go)]
-    got = Fn.attention_backward(*dev, heads)
-    for name, x, r, b in zip(("dq", "dk", "dv"), got, ref, base):
-        assert x.shape == r.shape and x.dtype == torch.float32 and x.is_contiguous() and r.numel() >= 64
-        err = (x.cpu().double() - r).abs().max().item()
-        print(f"shape {(Lq, Lk, B, heads, d)} {name}: err {err:.3e} fp32 CPU err {b:.3e} ratio {err / b:.2f}")
-    for x, r, b in zip(got, ref, base):
-        assert (x.cpu().double() - r).abs().max().item() <= 4 * b
-    again = Fn.attention_backward(*dev, heads)
+    got, _ = check_against_fp64(Fn.attention_backward, q, k, v, go, heads, label=f"shape {(Lq, Lk, B, heads, d)}",
+                                zero_error_takes_largest=False)
+    again = Fn.attention_backward(*(t.cuda() for t in (q, k, v, go)), heads)
     assert all(torch.equal(x, y) for x, y in zip(got, again))
 
 
@@ -108,7 +69,7 @@ def test_uniform_probabilities_are_exact(Fn, Lq):
     k = torch.randn(Lk, B, C, generator=gen)
     v = torch.randint(-3, 4, (Lk, B, C), generator=gen).float()
     go = torch.randint(-3, 4, (Lq, B, C), generator=gen).float()
-    ref = _cpu_grads(q, k, v, go, heads, torch.float64)
+    ref = cpu_grads(q, k, v, go, heads, torch.float64)
     dq, dk, dv = Fn.attention_backward(q.cuda(), k.cuda(), v.cuda(), go.cuda(), heads)
     assert torch.equal(dv.cpu(), ref[2].float())
     assert (dk == 0).all()
@@ -215,23 +176,6 @@ LATTICE_LK = {2: 64, 3: 64, 15: 64, 16: 64, 17: 64, 63: 64, 64: 64, 65: 128, 127
 LATTICE_LQ = [1, 15, 16, 17, 33]          # the 16-query chunk: below, at, one past, two chunks + 1
 
 
-def _check_against_fp64(Fn, q, k, v, go, heads, label):
-    """The file's yardstick on one set of inputs: every tensor within 4 x the worse fp32 CPU formulation's error against fp64
-    autograd.  A tensor whose fp32 CPU error is 0 (its exact gradient is 0) takes the largest fp32 CPU error of the three as baseline."""
-    ref, base = _bounds(q, k, v, go, heads)
-    base = [b if b > 0 else max(base) for b in base]
-    got = Fn.attention_backward(*(t.cuda() for t in (q, k, v, go)), heads)
-    errs = []
-    for name, x, r, b in zip(("dq", "dk", "dv"), got, ref, base):
-        assert x.shape == r.shape and x.dtype == torch.float32 and x.is_contiguous() and r.numel() >= 64
-        err = (x.cpu().double() - r).abs().max().item()
-        errs.append(err)
-        print(f"{label} {name}: err {err:.3e} fp32 CPU err {b:.3e} ratio {err / b:.2f}")
-    for name, err, b in zip(("dq", "dk", "dv"), errs, base):
-        assert err <= 4 * b, f"{label} {name}: err {err:.3e} > 4 x {b:.3e}"          # (NaN fails)
-    return got
-
-
 @pytest.mark.parametrize("d", [32, 64])
 @pytest.mark.parametrize("Lk", sorted(LATTICE_LK))
 def test_backward_lattice_of_thread_counts_and_chunk_edges(Fn, Lk, d):
@@ -244,7 +188,7 @@ def test_backward_lattice_of_thread_counts_and_chunk_edges(Fn, Lk, d):
     B, heads = 2, 2
     for Lq in LATTICE_LQ:
         q, k, v, go = _draw(Lq, Lk, B, heads, d, 31 + Lq)
-        _check_against_fp64(Fn, q, k, v, go, heads, f"lattice {(Lq, Lk, B, heads, d)}")
+        check_against_fp64(Fn.attention_backward, q, k, v, go, heads, label=f"lattice {(Lq, Lk, B, heads, d)}")
 
 
 @pytest.mark.parametrize("Lq,Lk,d", [(33, 256, 64), (100, 100, 32)])
@@ -259,7 +203,7 @@ def test_one_hot_attention_gradients_are_exact(Fn, Lq, Lk, d):
     for b in range(B):
         want_dv[:, b].index_add_(0, pi[b], go[:, b])
     assert any(pi[b].unique().numel() < Lq for b in range(B))
-    cq, ck, cv = _cpu_grads(q, k, v, go, heads, torch.float32)
+    cq, ck, cv = cpu_grads(q, k, v, go, heads, torch.float32)
     assert (cq == 0).all() and (ck == 0).all() and torch.equal(cv, want_dv)       # the reference alone meets the claim
     dq, dk, dv = (t.cpu() for t in Fn.attention_backward(q.cuda(), k.cuda(), v.cuda(), go.cuda(), heads))
     assert (dq == 0).all() and (dk == 0).all()
@@ -280,7 +224,7 @@ def test_backward_with_row_maxima_from_minus_900_to_plus_900_log2_units(Fn, Lq, 
     q, k, v = score_range_inputs(Lq, Lk, d, 51 + Lk)
     go = torch.randn(q.shape, generator=torch.Generator().manual_seed(52))
     assert_score_range(q, k, d)
-    _check_against_fp64(Fn, q, k, v, go, heads, f"score range {(Lq, Lk, d)}")
+    check_against_fp64(Fn.attention_backward, q, k, v, go, heads, label=f"score range {(Lq, Lk, d)}")
 
 
 def test_autograd_over_the_score_range(Fn):

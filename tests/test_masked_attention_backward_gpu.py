@@ -1,19 +1,17 @@
 """csrc/masked_attention_backward.hip: the gradients of softmax(q k^T / sqrt(d), blocked keys left out) v over long key sequences,
 their determinism, the mask semantics of the forward kernel, and the autograd wiring of functions.masked_attention.
 
-Yardstick: that of tests/test_attention_backward_gpu.py with the mask applied in all three CPU runs — fp64 autograd of
-``cpu_ops.attention(..., mask, allowed_count)`` on the CPU; per tensor the bound is 4 x the worse of two fp32 CPU formulations
-(torch's softmax, and exp2 on scores scaled by scale * log2(e)); a tensor whose fp32 CPU error is 0 takes the largest of the
-three.  It is never the kernel's own output.  Every compared tensor has at least 64 elements.
+Yardstick: tests/attention_backward_cases.py with the mask applied in all three CPU runs — per tensor 4 x the error of the worse of two
+fp32 CPU formulations against fp64 autograd of ``cpu_ops.attention(..., mask, allowed_count)``; a tensor whose fp32 CPU error is 0
+takes the largest of the three.  It is never the kernel's own output.  Every compared tensor has at least 64 elements.
 
 The lattice takes its key and query tiles from functions.masked_attention_backward_plan, the function the launch consults.  The
 exact cases (uniform probabilities over exactly 16 open keys; one-hot attention with the inputs of
 tests/test_attention_edges_gpu.py) first assert that the fp32 CPU reference alone meets their claim."""
-import math
-
 import pytest
 import torch
 
+from attention_backward_cases import check_against_fp64, cpu_grads, cuda, draw
 from test_attention_edges_gpu import assert_score_range, one_hot_inputs, one_hot_margin, score_range_inputs
 
 pytestmark = pytest.mark.gpu
@@ -36,66 +34,13 @@ def Fn():
     return functions
 
 
-def _draw(Lq, Lk, B, heads, d, seed, masked=True, open_fraction=0.25):
-    gen = torch.Generator().manual_seed(seed)
-    C = heads * d
-    q, k, v, go = (torch.randn(L, B, C, generator=gen) for L in (Lq, Lk, Lk, Lq))
-    mask = allowed = None
-    if masked:
-        mask = (torch.rand(B, Lq, Lk, generator=gen) >= open_fraction).to(torch.uint8)
-        allowed = (mask == 0).sum(-1).to(torch.int32)
-    return q, k, v, go, mask, allowed
-
-
-def _cpu_grads(q, k, v, go, heads, dtype, mask=None, allowed=None, base2=False):
-    """(dq, dk, dv) by torch autograd of the cpu_ops.attention composition in `dtype`; base2: the softmax as exp2 on scores scaled
-    by scale * log2(e), normalised by their sum (what the kernel computes)."""
-    from dvis_plus_amd import cpu_ops
-    q, k, v = (t.to(dtype).clone().requires_grad_() for t in (q, k, v))
-    if not base2:
-        out = cpu_ops.attention(q, k, v, heads, mask, allowed)
-    else:
-        Lq, B, C = q.shape
-        Lk, d = k.shape[0], C // heads
-        split = lambda t, n: t.reshape(n, B, heads, d).permute(1, 2, 0, 3)
-        s = (split(q, Lq) @ split(k, Lk).transpose(-1, -2)) * ((1.0 / d ** 0.5) * math.log2(math.e))
-        if mask is not None:
-            s = s.masked_fill((mask.bool() & (allowed > 0)[..., None])[:, None], float("-inf"))
-        e = torch.exp2(s - s.amax(-1, keepdim=True))
-        out = ((e / e.sum(-1, keepdim=True)) @ split(v, Lk)).permute(2, 0, 1, 3).reshape(Lq, B, C)
-    return torch.autograd.grad(out, (q, k, v), go.to(dtype))
-
-
-def _cuda(*ts):
-    return [None if t is None else t.cuda() for t in ts]
-
-
-def _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, label):
-    ref = _cpu_grads(q, k, v, go, heads, torch.float64, mask, allowed)
-    a = _cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed)
-    b = _cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed, base2=True)
-    base = [max((x.double() - r).abs().max().item(), (y.double() - r).abs().max().item()) for x, y, r in zip(a, b, ref)]
-    base = [e if e > 0 else max(base) for e in base]
-    dq, dk, dv, dgo, dm, da = _cuda(q, k, v, go, mask, allowed)
-    got = Fn.masked_attention_backward(dq, dk, dv, dgo, heads, dm, da)
-    errs = []
-    for name, x, r, e in zip(("dq", "dk", "dv"), got, ref, base):
-        assert x.shape == r.shape and x.dtype == torch.float32 and x.is_contiguous() and r.numel() >= 64
-        err = (x.cpu().double() - r).abs().max().item()
-        errs.append(err)
-        print(f"{label} {name}: err {err:.3e} fp32 CPU err {e:.3e} ratio {err / e if e else float(err > 0):.2f}")
-    for name, err, e in zip(("dq", "dk", "dv"), errs, base):
-        assert err <= 4 * e, f"{label} {name}: err {err:.3e} > 4 x {e:.3e}"          # (NaN fails)
-    return got, ref
-
-
 @pytest.mark.parametrize("Lq,Lk,B,heads,d,masked", SHAPES)
 def test_backward_against_fp64_and_determinism(Fn, Lq, Lk, B, heads, d, masked):
-    q, k, v, go, mask, allowed = _draw(Lq, Lk, B, heads, d, 61, masked)
+    q, k, v, go, mask, allowed = draw(Lq, Lk, B, heads, d, 61, masked)
     if masked:
         assert Lk < 64 or 0.2 < (mask == 0).float().mean().item() < 0.3
-    got, _ = _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, f"shape {(Lq, Lk, B, heads, d, masked)}")
-    again = Fn.masked_attention_backward(*_cuda(q, k, v, go), heads, *_cuda(mask, allowed))
+    got, _ = check_against_fp64(Fn.masked_attention_backward, q, k, v, go, heads, mask, allowed, f"shape {(Lq, Lk, B, heads, d, masked)}")
+    again = Fn.masked_attention_backward(*cuda(q, k, v, go), heads, *cuda(mask, allowed))
     assert all(torch.equal(x, y) for x, y in zip(got, again))
 
 
@@ -126,8 +71,8 @@ def test_backward_lattice_of_key_tiles_and_query_chunks(Fn, which, d):
     for Lq in [1, qt - 1, qt, qt + 1, 100] + ([256] if which == "kt" else []):
         plan = Fn.masked_attention_backward_plan(Lq, Lk, d)
         assert (plan.key_tile, plan.query_tile) == (kt, qt) and plan.n_key_tiles == -(-Lk // kt)
-        q, k, v, go, mask, allowed = _draw(Lq, Lk, B, heads, d, 71 + Lq, open_fraction=0.5)
-        _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, f"lattice {(Lq, Lk, B, heads, d)}")
+        q, k, v, go, mask, allowed = draw(Lq, Lk, B, heads, d, 71 + Lq, open_fraction=0.5)
+        check_against_fp64(Fn.masked_attention_backward, q, k, v, go, heads, mask, allowed, f"lattice {(Lq, Lk, B, heads, d)}")
 
 
 @pytest.mark.parametrize("Lq", [10, 17])
@@ -149,10 +94,10 @@ def test_uniform_probabilities_over_16_open_keys_are_exact(Fn, Lq):
     assert (allowed == 16).all() and not torch.equal(mask[0, 0], mask[0, 1])
     never = (mask == 1).all(1).T                                                   # (Lk, B): blocked for every query
     assert never.any() and (mask[:, :, :256] == 0).any() and (mask[:, :, 256:] == 0).any()
-    ref = _cpu_grads(q, k, v, go, heads, torch.float64, mask, allowed)
-    c32 = _cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed)
+    ref = cpu_grads(q, k, v, go, heads, torch.float64, mask, allowed)
+    c32 = cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed)
     assert torch.equal(c32[2], ref[2].float()) and (c32[1] == 0).all() and ref[1].abs().max().item() == 0
-    dq, dk, dv = (t.cpu() for t in Fn.masked_attention_backward(*_cuda(q, k, v, go), heads, *_cuda(mask, allowed)))
+    dq, dk, dv = (t.cpu() for t in Fn.masked_attention_backward(*cuda(q, k, v, go), heads, *cuda(mask, allowed)))
     assert torch.equal(dv, ref[2].float())
     assert (dk == 0).all()
     assert (dv[never] == 0).all() and (dk[never] == 0).all()
@@ -175,22 +120,22 @@ def test_one_hot_attention_gradients_are_exact(Fn, Lq, Lk, d):
     want_dv = torch.zeros(Lk, B, heads * d)
     for b in range(B):
         want_dv[:, b].index_add_(0, pi[b], go[:, b])
-    cq, ck, cv = _cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed)
+    cq, ck, cv = cpu_grads(q, k, v, go, heads, torch.float32, mask, allowed)
     assert (cq == 0).all() and (ck == 0).all() and torch.equal(cv, want_dv)       # the reference alone meets the claim
-    dq, dk, dv = (t.cpu() for t in Fn.masked_attention_backward(*_cuda(q, k, v, go), heads, *_cuda(mask, allowed)))
+    dq, dk, dv = (t.cpu() for t in Fn.masked_attention_backward(*cuda(q, k, v, go), heads, *cuda(mask, allowed)))
     assert (dq == 0).all() and (dk == 0).all()
     assert torch.equal(dv, want_dv)
 
 
 def test_a_row_with_count_zero_ignores_its_mask(Fn):
     Lq, Lk, B, heads, d = 20, 300, 2, 2, 32
-    q, k, v, go, _, _ = _draw(Lq, Lk, B, heads, d, 101, masked=False)
+    q, k, v, go, _, _ = draw(Lq, Lk, B, heads, d, 101, masked=False)
     mask = torch.zeros(B, Lq, Lk, dtype=torch.uint8)
     mask[1, 7] = 1
     allowed = (mask == 0).sum(-1).to(torch.int32)
     assert allowed[1, 7] == 0 and (allowed > 0).sum() == B * Lq - 1
-    dev = _cuda(q, k, v, go)
-    dmask, dallowed = _cuda(mask, allowed)
+    dev = cuda(q, k, v, go)
+    dmask, dallowed = cuda(mask, allowed)
     plain = Fn.masked_attention_backward(*dev, heads)
     got = Fn.masked_attention_backward(*dev, heads, dmask, dallowed)
     assert torch.equal(got[0][7, 1], plain[0][7, 1])
@@ -199,16 +144,16 @@ def test_a_row_with_count_zero_ignores_its_mask(Fn):
 
 def test_blocking_a_key_removes_its_contribution_from_the_row(Fn):
     Lq, Lk, B, heads, d = 5, 300, 2, 2, 32
-    q, k, v, go, mask, allowed = _draw(Lq, Lk, B, heads, d, 111)
+    q, k, v, go, mask, allowed = draw(Lq, Lk, B, heads, d, 111)
     b0, r0, j = 1, 3, 277                      # key j of batch entry b0: open for row r0 alone
     mask[b0, :, j] = 1
     mask[b0, r0, j] = 0
     allowed = (mask == 0).sum(-1).to(torch.int32)
-    before, _ = _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, "one open row")
+    before, _ = check_against_fp64(Fn.masked_attention_backward, q, k, v, go, heads, mask, allowed, "one open row")
     assert before[1][j, b0].abs().max() > 0 and before[2][j, b0].abs().max() > 0
     mask[b0, r0, j] = 1
     allowed = (mask == 0).sum(-1).to(torch.int32)
-    after, ref = _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, "blocked for every row")
+    after, ref = check_against_fp64(Fn.masked_attention_backward, q, k, v, go, heads, mask, allowed, "blocked for every row")
     assert ref[1][j, b0].abs().max() == 0 and ref[2][j, b0].abs().max() == 0
     assert (after[1][j, b0] == 0).all() and (after[2][j, b0] == 0).all()
     assert torch.equal(after[2][:, 0], before[2][:, 0])                            # the other batch entry: untouched
@@ -229,7 +174,7 @@ def test_backward_with_row_maxima_from_minus_900_to_plus_900_log2_units(Fn, Lq, 
     assert_score_range(q, k, d, mask)
     mask = mask.to(torch.uint8)
     allowed = (mask == 0).sum(-1).to(torch.int32)
-    _check_against_fp64(Fn, q, k, v, go, heads, mask, allowed, f"score range {(Lq, Lk, d)}")
+    check_against_fp64(Fn.masked_attention_backward, q, k, v, go, heads, mask, allowed, f"score range {(Lq, Lk, d)}")
 
 
 def test_views_are_bit_equal_to_contiguous_copies(Fn):
@@ -263,7 +208,7 @@ def test_views_are_bit_equal_to_contiguous_copies(Fn):
 
 def test_a_batch_entry_does_not_depend_on_its_batch(Fn):
     Lq, Lk, B, heads, d = 40, 600, 8, 2, 32
-    q, k, v, go, mask, allowed = _cuda(*_draw(Lq, Lk, B, heads, d, 141))
+    q, k, v, go, mask, allowed = cuda(*draw(Lq, Lk, B, heads, d, 141))
     full = Fn.masked_attention_backward(q, k, v, go, heads, mask, allowed)
     for b in (0, 5):
         alone = Fn.masked_attention_backward(*(t[:, b:b + 1].contiguous() for t in (q, k, v, go)), heads, mask[b:b + 1].contiguous(),
@@ -275,7 +220,7 @@ def test_a_batch_entry_does_not_depend_on_its_batch(Fn):
 @pytest.mark.parametrize("masked", [True, False])
 def test_autograd_wiring(Fn, needs, masked):
     Lq, Lk, B, heads, d = 21, 300, 3, 2, 32
-    q, k, v, go, mask, allowed = _cuda(*_draw(Lq, Lk, B, heads, d, 151, masked))
+    q, k, v, go, mask, allowed = cuda(*draw(Lq, Lk, B, heads, d, 151, masked))
     with torch.no_grad():
         plain = Fn.attention(q, k, v, heads, mask, allowed)
         assert torch.equal(Fn.masked_attention(q, k, v, heads, mask, allowed), plain)
@@ -293,7 +238,7 @@ def test_autograd_wiring(Fn, needs, masked):
 def test_backward_copies_a_gradient_that_misses_the_view_contract(Fn):
     """The upstream gradient of a concatenation on the last dim is a narrowed view one float past a 16-byte boundary."""
     Lq, Lk, B, heads, d = 8, 300, 2, 2, 32
-    q, k, v, go, mask, allowed = _cuda(*_draw(Lq, Lk, B, heads, d, 161))
+    q, k, v, go, mask, allowed = cuda(*draw(Lq, Lk, B, heads, d, 161))
     leaves = [t.clone().requires_grad_() for t in (q, k, v)]
     out = torch.cat([torch.zeros(Lq, B, 1, device="cuda"), Fn.masked_attention(*leaves, heads, mask, allowed)], dim=-1)
     wide = torch.cat([torch.zeros(Lq, B, 1, device="cuda"), go], dim=-1)
@@ -303,7 +248,7 @@ def test_backward_copies_a_gradient_that_misses_the_view_contract(Fn):
 
 
 def test_bool_masks_are_read_as_uint8(Fn):
-    q, k, v, go, mask, allowed = _cuda(*_draw(6, 35, 2, 2, 32, 171))
+    q, k, v, go, mask, allowed = cuda(*draw(6, 35, 2, 2, 32, 171))
     want = Fn.masked_attention_backward(q, k, v, go, 2, mask, allowed)
     got = Fn.masked_attention_backward(q, k, v, go, 2, mask.bool(), allowed)
     assert all(torch.equal(x, y) for x, y in zip(got, want))
