@@ -57,6 +57,13 @@ class ConvBN(nn.Conv2d):
         """Is `t` the folded weight of this layer (the range guard names a layer by the weight it packed)?"""
         return self._folded.value is not None and self._folded.value[0] is t
 
+    def live(self, x):
+        """The layer under autograd (ResNet._forward_live): the library convolution on the LIVE weight, then the FrozenBN affine from
+        the buffers — nothing folded, nothing cached, so the weight gets its gradient."""
+        scale, shift = self.norm.scale_shift()
+        y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation, self.groups)
+        return y * scale.reshape(1, -1, 1, 1) + shift.reshape(1, -1, 1, 1)
+
     def forward(self, x, res=None, relu=False):
         """conv (MIOpen, no bias) then ONE fused pass: + folded-BN shift (+ residual) (+ ReLU)."""
         w, b = self.folded()
@@ -208,8 +215,25 @@ class ResNet(nn.Module):
             blocks.append(dict(w1=w1, b1=b1, w2=w2, b2=b2, w3=w3, b3=b3, ws=ws, bs=bs))
         return blocks
 
+    def _forward_live(self, x):
+        """The backbone as torch ops on live weights: conv2d, the FrozenBN affine, ReLU, the stem's 3x3 / 2 max-pool, residual adds.
+        Library convolutions (MIOpen forward and backward on the GPU); the backward on own kernels is not built."""
+        out = {}
+        x = F.max_pool2d(F.relu(self.stem.conv1.live(x)), kernel_size=3, stride=2, padding=1)
+        for name in self.stage_names:
+            for b in getattr(self, name):
+                y = F.relu(b.conv2.live(F.relu(b.conv1.live(x))))
+                x = F.relu(b.conv3.live(y) + (x if b.shortcut is None else b.shortcut.live(x)))
+            if name in self._out_features:
+                out[name] = x
+        return out
+
     @Fn.fp32_island
     def forward(self, x):
+        """Under autograd with any trainable parameter: `_forward_live`.  The path below multiplies by folded, DETACHED weights —
+        a backward through it would reach no parameter, silently; with every parameter frozen, or under no_grad, it is the path."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self._forward_live(Fn.f32(x))
         out = {}
         x = self.stem(Fn.f32(x))
         for name in self.stage_names:

@@ -257,6 +257,125 @@ def msda_fused_forward(value, spatial_shapes, level_start_index, reference_point
     return out
 
 
+def msda_fused_backward_ok(x, head_dim, n_levels, n_points):
+    """The domain of ``msda_fused_backward`` (the fused forward's fp32 domain) for projections of the tensor `x`: the caller's
+    dispatch test — outside it the unfused ``MSDeformAttnFunction`` is the op under autograd."""
+    return (x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled() and head_dim in (32, 64)
+            and (n_levels, n_points) in ((1, 4), (3, 4), (4, 4)))
+
+
+def msda_fused_backward(value, spatial_shapes, level_start_index, reference_points, offsets, logits, grad_out, n_levels,
+                        n_points, deterministic=None):
+    """Backward of ``msda_fused_forward`` in its fp32 domain (D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, no slots / head-major
+    value / position rows) -> (grad_value (N,S,M,D), grad_offsets (N*Lq, M*L*P*2), grad_logits (N*Lq, M*L*P)).  The inputs are
+    the forward's own — the RAW row views — and the kernel recomputes softmax and locations: no (N, Lq, M, L, P, 3) tensor is
+    read or written.  The reference points get no gradient.  deterministic: as ``ms_deform_attn_backward`` (grad_offsets /
+    grad_logits are the same bits either way)."""
+    if value.dim() != 4:
+        raise RuntimeError("msda_fused_backward: value must be (N, S, M, D)")
+    N, S, M, D = value.shape
+    L, P = int(n_levels), int(n_points)
+    if reference_points.requires_grad:
+        raise RuntimeError("msda_fused_backward: the reference points get no gradient (requires_grad is set)")
+    if reference_points.dim() != 4 or reference_points.shape[2:] != (L, 2) or reference_points.shape[0] not in (1, N):
+        raise RuntimeError("msda_fused_backward: reference_points must be (1|N, Lq, L, 2)")
+    nref, Lq = reference_points.shape[0], reference_points.shape[1]
+    for name, t in (("value", value), ("reference_points", reference_points), ("spatial_shapes", spatial_shapes),
+                    ("level_start_index", level_start_index)):
+        native.dev_ptr(t, name)
+    if value.dtype != torch.float32 or reference_points.dtype != torch.float32:
+        raise RuntimeError("msda_fused_backward: fp32 only")
+    if D not in (32, 64) or (L, P) not in ((1, 4), (3, 4), (4, 4)):
+        raise RuntimeError(f"msda_fused_backward: unsupported (D={D}, L={L}, P={P}); supported D in {{32,64}}, "
+                           "(L,P) in {(1,4),(3,4),(4,4)}")
+    for name, t, width in (("offsets", offsets, M * L * P * 2), ("logits", logits, M * L * P)):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != N * Lq \
+                or t.shape[1] < width:
+            raise RuntimeError(f"{name} must be a float32 GPU (N*Lq, >= {width}) row view with unit inner stride")
+        if t.data_ptr() % 16 or (t.shape[0] > 1 and t.stride(0) % 4):
+            raise RuntimeError(f"msda_fused_backward: {name} rows must be 16-byte aligned (row stride a multiple of 4 floats)")
+    if not grad_out.is_cuda or grad_out.dtype != torch.float32 or grad_out.numel() != N * Lq * M * D:
+        raise RuntimeError("grad_out must be a float32 GPU (N, Lq, M*D) tensor")
+    grad_out = grad_out.contiguous()
+    if deterministic is None:
+        deterministic = (MSDA_BWD_DETERMINISTIC == "1") if MSDA_BWD_DETERMINISTIC in ("0", "1") \
+            else torch.are_deterministic_algorithms_enabled()
+    grad_value = torch.empty_like(value, memory_format=torch.contiguous_format)
+    grad_off = torch.empty((N * Lq, M * L * P * 2), dtype=torch.float32, device=value.device)
+    grad_logit = torch.empty((N * Lq, M * L * P), dtype=torch.float32, device=value.device)
+    ws = None
+    if deterministic:
+        nbytes = native.lib().dvis_msda_fused_backward_ws_bytes(N, S, M, D)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=value.device)
+    with torch.cuda.device(value.device):
+        rc = native.lib().dvis_msda_fused_backward(
+            native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
+            native.dev_ptr(level_start_index, "level_start_index"), native.dev_ptr(reference_points, "ref"), nref,
+            ctypes.c_void_p(offsets.data_ptr()), offsets.stride(0), ctypes.c_void_p(logits.data_ptr()), logits.stride(0),
+            native.dev_ptr(grad_out, "grad_out"), N, S, M, D, L, Lq, P, native.dev_ptr(grad_value, "grad_value"),
+            native.dev_ptr(grad_off, "grad_offsets"), native.dev_ptr(grad_logit, "grad_logits"),
+            None if ws is None else ctypes.c_void_p(ws.data_ptr()), native.stream_ptr(value.device))
+    native.check(rc, "dvis_msda_fused_backward")
+    return grad_value, grad_off, grad_logit
+
+
+class MSDAFusedFunction(Function):
+    """``msda_fused_forward`` under autograd: saves value, the two raw row views and the reference points — no locations, no
+    weights, no output — and ``msda_fused_backward`` recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, value, offsets, logits, spatial_shapes, level_start_index, reference_points, n_levels, n_points,
+                shapes_host):
+        ctx.n_levels, ctx.n_points = n_levels, n_points
+        out = msda_fused_forward(value, spatial_shapes, level_start_index, reference_points, offsets, logits, n_levels,
+                                 n_points, shapes_host)
+        ctx.save_for_backward(value, offsets, logits, spatial_shapes, level_start_index, reference_points)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        value, offsets, logits, shapes, level_start, ref = ctx.saved_tensors
+        gv, go, gl = msda_fused_backward(value, shapes, level_start, ref, offsets, logits, grad_out, ctx.n_levels, ctx.n_points)
+        M, LP = value.shape[2], ctx.n_levels * ctx.n_points
+        # the row views may be wider than a head run (slices of one projection): the gradient has the view's shape
+        if offsets.shape[1] != M * LP * 2:
+            go = torch.nn.functional.pad(go, (0, offsets.shape[1] - M * LP * 2))
+        if logits.shape[1] != M * LP:
+            gl = torch.nn.functional.pad(gl, (0, logits.shape[1] - M * LP))
+        return gv, go, gl, None, None, None, None, None, None
+
+
+def _msda_fused_torch(value, spatial_shapes, reference_points, offsets, logits, L, P):
+    """The torch formulation of the fused op (ops/modules/ms_deform_attn.py:101-117) for CPU tensors."""
+    N, S, M, D = value.shape
+    Lq = reference_points.shape[1]
+    off = offsets[:, :M * L * P * 2].reshape(N, Lq, M, L, P, 2)
+    w = torch.softmax(logits[:, :M * L * P].reshape(N, Lq, M, L * P), -1).view(N, Lq, M, L, P)
+    norm = torch.stack([spatial_shapes[..., 1], spatial_shapes[..., 0]], -1).to(value.dtype)
+    loc = reference_points[:, :, None, :, None, :] + off / norm[None, None, None, :, None, :]
+    return cpu_ops.ms_deform_attn_core_pytorch(value, spatial_shapes, loc.expand(N, -1, -1, -1, -1, -1), w)
+
+
+def msda_fused(value, spatial_shapes, level_start_index, reference_points, offsets, logits, n_levels, n_points,
+               shapes_host=None):
+    """``msda_fused_forward`` that also trains: without a requires-grad input it IS that call (the same bits); with one it is
+    ``MSDAFusedFunction`` (forward = that same call, backward = ``msda_fused_backward``).  CPU tensors take the torch
+    formulation and torch's autograd.  A ``reference_points`` that requires grad raises: the kernel has no gradient for it."""
+    if reference_points.requires_grad:
+        raise RuntimeError("msda_fused: reference_points must not require grad (the fused backward has no gradient for them)")
+    if _on_cpu(value, offsets, logits, reference_points):
+        return _msda_fused_torch(value, spatial_shapes, reference_points, offsets, logits, n_levels, n_points)
+    if not (torch.is_grad_enabled() and (value.requires_grad or offsets.requires_grad or logits.requires_grad)):
+        return msda_fused_forward(value, spatial_shapes, level_start_index, reference_points, offsets, logits, n_levels,
+                                  n_points, shapes_host)
+    if not (msda_fused_backward_ok(value, value.shape[3], n_levels, n_points) and offsets.dtype == logits.dtype == torch.float32):
+        raise RuntimeError("msda_fused: under autograd only the fp32 domain of msda_fused_backward is served (D in {32,64}, "
+                           "(L,P) in {(1,4),(3,4),(4,4)}); use MSDeformAttnFunction")
+    return MSDAFusedFunction.apply(value, offsets, logits, spatial_shapes, level_start_index, reference_points,
+                                   int(n_levels), int(n_points), shapes_host)
+
+
 def _on_cpu(*tensors):
     """Every tensor lives on the CPU: the call takes the torch formulation of cpu_ops.py (BASELINE config #1, "PyTorch CPU
     MSDeformAttn fallback (plumbing, no GPU)").  Decided by DEVICE alone: a GPU tensor never ends up there — the HIP kernel runs

@@ -229,6 +229,27 @@ class _VideoBase(nn.Module):
             x = torch.nn.functional.pad(x, (0, Wp - W, 0, Hp - H))
         return x, (H, W)
 
+    def prepare_targets(self, batched_inputs, images):
+        """meta_architecture.py:328-360 (MinVIS), the same code in the tracker and refiner stages.  "instances": one object per
+        frame with gt_ids (N), gt_classes (N) and gt_masks (N, h, w) as a tensor or an object with `.tensor`; read by attribute,
+        so detectron2's Instances or any stand-in does."""
+        Hp, Wp = images.shape[-2:]
+        out = []
+        for video in batched_inputs:
+            frames = video["instances"]
+            masks = torch.zeros((len(frames[0].gt_ids), len(frames), Hp, Wp), dtype=torch.bool, device=self.device)
+            ids, classes = [], []
+            for f, inst in enumerate(frames):
+                m = getattr(inst.gt_masks, "tensor", inst.gt_masks).to(self.device)
+                masks[:, f, :m.shape[-2], :m.shape[-1]] = m.bool()
+                ids.append(inst.gt_ids.to(self.device)[:, None])
+                classes.append(inst.gt_classes.to(self.device)[:, None])
+            ids = torch.cat(ids, dim=1)
+            classes = torch.cat(classes, dim=1).max(dim=1)[0]
+            valid = (ids != -1).any(dim=-1)
+            out.append({"labels": classes[valid], "ids": ids[valid], "masks": masks[valid].float()})
+        return out
+
     def encode(self, images):
         """Backbone + pixel decoder over this rank's frames: (multi_scale_features, mask_features (t,Cm,h,w))."""
         chunk = segmenter_frames_per_call(len(images), images.shape[-2], images.shape[-1], self.segmenter_chunk)
@@ -346,12 +367,56 @@ class MinVIS(_VideoBase):
         """meta_architecture.py:91-181."""
         ret = cls._common_from_config(cfg)
         ret["task"] = "vis"
+        from .criterion import build_criterion
+        # an inference-only config may leave the loss keys out: such a model has no criterion and .train() calls raise
+        if "CLASS_WEIGHT" in cfg.MODEL.MASK_FORMER:
+            ret["criterion"] = build_criterion(cfg, "MinVIS")
         return ret
 
-    @torch.no_grad()
-    @Fn.fp32_island
     def forward(self, batched_inputs):
-        assert len(batched_inputs) == 1 and not self.training
+        """.eval(): the reference's output dict of one video.  .train(): the weighted loss dict of the segmenter stage."""
+        if self.training:
+            return self._forward_train(batched_inputs)
+        with torch.no_grad():
+            return self._forward_eval(batched_inputs)
+
+    # ---- training (meta_architecture.py:182-209): backbone, pixel decoder and decoder all train, every frame is a target
+    @Fn.fp32_island
+    def _forward_train(self, batched_inputs):
+        if self.criterion is None:
+            raise RuntimeError("MinVIS.train() needs a criterion (from_config builds it; criterion.build_criterion)")
+        if self.clip_shard.world > 1:
+            raise RuntimeError("MinVIS.train(): multi-GPU training is not built; train on one GPU")
+        frames = [f for video in batched_inputs for f in video["image"]]
+        if len({tuple(f.shape[-2:]) for f in frames}) != 1:
+            raise ValueError("MinVIS.train(): every frame of the batch must have one size (the data loader's crop); got "
+                             f"{sorted({tuple(f.shape[-2:]) for f in frames})}")
+        images, _ = self.preprocess(frames)                 # all frames of all videos: (b t) frames, t = num_frames
+        with Fn.x3_stage("backbone"):
+            features = self.backbone(images)
+        outputs = self.sem_seg_head(features)
+        targets = self.prepare_targets(batched_inputs, images)
+        outputs, targets = self.frame_decoder_loss_reshape(outputs, targets)
+        losses = self.criterion(outputs, targets)
+        weights = self.criterion.weight_dict
+        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+
+    @staticmethod
+    def frame_decoder_loss_reshape(outputs, targets):
+        """Every labelled frame becomes a batch entry of one frame (meta_architecture.py:234-253)."""
+        def one(d):
+            return {"pred_masks": d["pred_masks"].permute(0, 2, 1, 3, 4).flatten(0, 1).unsqueeze(2),       # b q t h w -> (b t) q 1 h w
+                    "pred_logits": d["pred_logits"].flatten(0, 1)}                                       # b t q c -> (b t) q c
+        out = {**outputs, **one(outputs)}
+        if "aux_outputs" in outputs:
+            out["aux_outputs"] = [one(a) for a in outputs["aux_outputs"]]
+        per_frame = [{"labels": t["labels"], "ids": t["ids"][:, [f]], "masks": t["masks"][:, [f]]}
+                     for t in targets for f in range(t["ids"].shape[1])]
+        return out, per_frame
+
+    @Fn.fp32_island
+    def _forward_eval(self, batched_inputs):
+        assert len(batched_inputs) == 1
         from . import functions as Fn
         from .tracker import match_chain
         video = batched_inputs[0]
@@ -363,7 +428,7 @@ class MinVIS(_VideoBase):
         try:
             self._guard_verify(self._guard_snapshot())
         except Fn.X3RangeError as e:
-            return self._x3_rerun(e, lambda: self.forward(batched_inputs))
+            return self._x3_rerun(e, lambda: self._forward_eval(batched_inputs))
         T, Q, _ = dec.shape
         # ---- alignment chain: frame 0 keeps its order, frame t is matched to the ALIGNED frame t-1
         idx = torch.arange(Q, device=dec.device).unsqueeze(0).repeat(T, 1)
@@ -464,26 +529,6 @@ class DVIS_Plus_online(_VideoBase):
         ar = torch.arange(idx.shape[0], device=idx.device)[:, None]
         return {k: v[ar, idx] for k, v in output.items()}
 
-    def prepare_targets(self, batched_inputs, images):
-        """meta_architecture.py:328-360.  "instances": one object per frame with gt_ids (N), gt_classes (N) and gt_masks (N, h, w)
-        as a tensor or an object with `.tensor`; read by attribute, so detectron2's Instances or any stand-in does."""
-        Hp, Wp = images.shape[-2:]
-        out = []
-        for video in batched_inputs:
-            frames = video["instances"]
-            masks = torch.zeros((len(frames[0].gt_ids), len(frames), Hp, Wp), dtype=torch.bool, device=self.device)
-            ids, classes = [], []
-            for f, inst in enumerate(frames):
-                m = getattr(inst.gt_masks, "tensor", inst.gt_masks).to(self.device)
-                masks[:, f, :m.shape[-2], :m.shape[-1]] = m.bool()
-                ids.append(inst.gt_ids.to(self.device)[:, None])
-                classes.append(inst.gt_classes.to(self.device)[:, None])
-            ids = torch.cat(ids, dim=1)
-            classes = torch.cat(classes, dim=1).max(dim=1)[0]
-            valid = (ids != -1).any(dim=-1)
-            out.append({"labels": classes[valid], "ids": ids[valid], "masks": masks[valid].float()})
-        return out
-
     @staticmethod
     def frame_decoder_loss_reshape(outputs, targets, image_outputs=None):
         """Every frame becomes a batch entry of one frame (meta_architecture.py:716-740)."""
@@ -575,7 +620,6 @@ class DVIS_Plus_offline(_VideoBase):
                 p.requires_grad_(False)
         self.classes_references_memory = Outputs_Memory_PerClasses(max_len=20)
 
-    prepare_targets = DVIS_Plus_online.prepare_targets
     _get_instance_labels = staticmethod(DVIS_Plus_online._get_instance_labels)
 
     # ---- training (meta_architecture.py:1264-1375): frozen segmenter and tracker under no_grad, trainable refiner

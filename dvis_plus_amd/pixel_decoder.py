@@ -268,6 +268,25 @@ class MSDeformAttn(nn.Module):
                                                    self.im2col_step)
         return self.output_proj(output)
 
+    def train_forward(self, query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
+                      spatial_shapes_py=None):
+        """The reference's forward (ms_deform_attn.py:83-125, no padding mask) on LIVE weights under autograd: three
+        ``F.linear`` projections, then ``Fn.msda_fused`` — softmax, locations and the op in one kernel whose backward
+        recomputes them from the raw rows (no (N, Lq, M, L, P, 3) tensor is saved) — where its domain holds (fp32 on the
+        GPU, d in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, 2-d reference points); everything else takes the unfused branch
+        of ``_forward`` (``MSDeformAttnFunction``, the torch formulation on the CPU)."""
+        N, Len_q, _ = query.shape
+        M, L, P = self.n_heads, self.n_levels, self.n_points
+        if reference_points.shape[-1] == 2 and Fn.msda_fused_backward_ok(input_flatten, self.d_model // M, L, P):
+            value = F.linear(input_flatten, self.value_proj.weight, self.value_proj.bias).view(N, input_flatten.shape[1], M, -1)
+            offsets = F.linear(query, self.sampling_offsets.weight, self.sampling_offsets.bias).view(N * Len_q, -1)
+            logits = F.linear(query, self.attention_weights.weight, self.attention_weights.bias).view(N * Len_q, -1)
+            output = Fn.msda_fused(value, input_spatial_shapes, input_level_start_index, reference_points.contiguous(),
+                                   offsets, logits, L, P, shapes_host=spatial_shapes_py)
+            return F.linear(output, self.output_proj.weight, self.output_proj.bias)
+        return self._forward(query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index, None,
+                             spatial_shapes_py, None, None)
+
 
 class MSDeformAttnTransformerEncoderLayer(nn.Module):
     def __init__(self, d_model=256, d_ffn=1024, dropout=0.1, activation="relu", n_levels=4, n_heads=8, n_points=4):
@@ -313,6 +332,17 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
             return Fn.add_layer_norm(src2, src, self.norm2, pos=pos)
         out = Fn.add_layer_norm(src2, src, self.norm2)
         return (out, None) if emit_next_query else out
+
+    def train_forward(self, src, pos, reference_points, spatial_shapes, level_start_index, shapes_py=None):
+        """msdeformattn.py:116-131 as torch ops on live weights; dropout in the reference's three places (p = 0 in every
+        DVIS++ config)."""
+        drop = lambda t: F.dropout(t, self.dropout_p, training=True) if self.dropout_p else t
+        src2 = self.self_attn.train_forward(src if pos is None else src + pos, reference_points, src, spatial_shapes,
+                                            level_start_index, shapes_py)
+        src = F.layer_norm(src + drop(src2), self.norm1.normalized_shape, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        src2 = F.linear(drop(F.relu(F.linear(src, self.linear1.weight, self.linear1.bias))), self.linear2.weight,
+                        self.linear2.bias)
+        return F.layer_norm(src + drop(src2), self.norm2.normalized_shape, self.norm2.weight, self.norm2.bias, self.norm2.eps)
 
 
 class MSDeformAttnTransformerEncoder(nn.Module):
@@ -409,6 +439,21 @@ class MSDeformAttnTransformerEncoderOnly(nn.Module):
         memory = self.encoder(src_flatten, spatial_shapes, level_start_index, None, lvl_pos, None, shapes_py=shapes_py,
                               query0=query0)
         return memory, spatial_shapes, level_start_index, shapes_py
+
+    def train_forward(self, srcs, pos_embeds):
+        """msdeformattn.py:61-89 without padding masks (valid ratios are 1): nothing weight-derived is cached, `level_embed`
+        is live.  -> (memory, shapes_py)"""
+        shapes_py = [(int(s.shape[2]), int(s.shape[3])) for s in srcs]
+        dtype = srcs[0].dtype
+        src_flatten = torch.cat([s.flatten(2).transpose(1, 2) for s in srcs], 1)
+        lvl_pos = torch.cat([p.to(dtype).flatten(2).transpose(1, 2) + self.level_embed[lvl].view(1, 1, -1)
+                             for lvl, p in enumerate(pos_embeds)], 1)
+        spatial_shapes, level_start_index = self._shape_tensors(shapes_py, src_flatten.device)
+        ref = self.encoder.reference_points_unpadded(shapes_py, src_flatten.device).to(dtype)
+        output = src_flatten
+        for layer in self.encoder.layers:
+            output = layer.train_forward(output, lvl_pos, ref, spatial_shapes, level_start_index, shapes_py)
+        return output, shapes_py
 
 
 class ConvNorm(nn.Conv2d):
@@ -559,8 +604,10 @@ class MSDeformAttnPixelDecoder(nn.Module):
 
     def forward_features(self, features):
         """features: dict name -> (N, C, H, W).  fp32 island like the reference (msdeformattn.py:314-320).
-        Returns (mask_features, out[0], multi_scale_features[:3])."""
+        Returns (mask_features, out[0], multi_scale_features[:3]).  Under ``.train()``: ``_train_features``."""
         with torch.autocast(device_type="cuda", enabled=False), Fn.x3_stage("pd_proj"):
+            if self.training:
+                return self._train_features(features)
             srcs, pos, affines = [], [], []
             for idx, f in enumerate(self.transformer_in_features[::-1]):
                 x = features[f].float().contiguous()      # (a backbone may hand over channels-last strided maps)
@@ -604,6 +651,40 @@ class MSDeformAttnPixelDecoder(nn.Module):
                 multi_scale_features = TokenMaps(out[:self.maskformer_num_feature_levels])
                 multi_scale_features.tokens = tokens[:self.maskformer_num_feature_levels]
                 return self.mask_features(out[-1], in_affine=deferred), out[0], multi_scale_features
+
+    @staticmethod
+    def _conv_norm(layer, x):
+        """A ConvNorm as torch ops on live weights: conv2d -> GroupNorm -> activation."""
+        x = F.conv2d(x, layer.weight, layer.bias, layer.stride, layer.padding, layer.dilation, layer.groups)
+        if layer.norm is not None:
+            x = F.group_norm(x, layer.norm.num_groups, layer.norm.weight, layer.norm.bias, layer.norm.eps)
+        return x if layer.activation is None else layer.activation(x)
+
+    def _train_features(self, features):
+        """The reference's forward_features (msdeformattn.py:314-358) under autograd, nothing weight-derived cached: torch
+        ops on live weights everywhere except the encoder's sampling op (``MSDeformAttn.train_forward``).  Gradients reach
+        every parameter and the input maps.  The maps come back as plain tensors (a TokenMaps without token views: the
+        training decoders read the maps).  A float64 module stays float64."""
+        dtype = self.mask_features.weight.dtype
+        cast = lambda t: t.to(dtype) if dtype == torch.float64 else t.float()
+        srcs, pos = [], []
+        for idx, f in enumerate(self.transformer_in_features[::-1]):
+            x = cast(features[f])
+            conv, gn = self.input_proj[idx][0], self.input_proj[idx][1]
+            s_ = F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
+            srcs.append(F.group_norm(s_, gn.num_groups, gn.weight, gn.bias, gn.eps))
+            pos.append(self.pe_layer.compute(x.shape[2], x.shape[3], x.device))
+        y, shapes_py = self.transformer.train_forward(srcs, pos)
+        bs = y.shape[0]
+        out, start = [], 0
+        for h, w in shapes_py:
+            out.append(y[:, start:start + h * w].transpose(1, 2).reshape(bs, -1, h, w))
+            start += h * w
+        for idx, f in enumerate(self.in_features[:self.num_fpn_levels][::-1]):
+            cur_fpn = self._conv_norm(self.lateral_convs[idx], cast(features[f]))
+            top = F.interpolate(out[-1], size=cur_fpn.shape[-2:], mode="bilinear", align_corners=False)
+            out.append(self._conv_norm(self.output_convs[idx], cur_fpn + top))
+        return self._conv_norm(self.mask_features, out[-1]), out[0], TokenMaps(out[:self.maskformer_num_feature_levels])
 
 
 class TokenMaps(list):

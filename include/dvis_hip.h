@@ -160,6 +160,25 @@ int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int
                             const int64_t *shapes_host, void *stream);
 
 /*
+ * Backward of dvis_msda_fused_forward (fp32; the reference's row layout only: no slots, no head-major value, no position rows;
+ * D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, the forward's stride / alignment / 2 GiB requirements, Nref in {1, N} — anything
+ * else is an error code before a launch).  Inputs are the forward's own plus grad_out (N, Lq, M*D) contiguous; the kernel recomputes
+ * the softmax and the sampling locations per (n, q, m), so neither they nor their gradients exist in memory.
+ *   grad_value   (N, S, M, D), fully written by the call
+ *   grad_offsets (N*Lq, M*L*P*2) contiguous: d loss / d raw offset
+ *   grad_logits  (N*Lq, M*L*P)   contiguous: d loss / d raw logit (through the softmax)
+ * The reference points get no gradient.  ws == NULL: grad_value through float atomics.  ws = dvis_msda_fused_backward_ws_bytes bytes,
+ * 16-byte aligned: the 64-bit fixed-point form of dvis_msda_backward_det, its scale from max |grad_out| alone (softmaxed weights
+ * are <= 1); a non-finite grad_out, or a NaN / +Inf logit, comes back as NaN grad_value.  grad_offsets / grad_logits are the same
+ * bits in both forms.
+ */
+int64_t dvis_msda_fused_backward_ws_bytes(int N, int S, int M, int D);
+int dvis_msda_fused_backward(const float *value, const int64_t *shapes, const int64_t *level_start, const float *ref, int Nref,
+                             const float *offsets, int64_t off_stride, const float *logits, int64_t logit_stride,
+                             const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P, float *grad_value,
+                             float *grad_offsets, float *grad_logits, void *ws, void *stream);
+
+/*
  * Same, plus the projection of the queries' POSITION embedding: MSDeformAttn is called with query = src + pos
  * (pixel_decoder/msdeformattn.py:124-126) and only the two linears above read the query, so
  * linear(src + pos) = linear(src) + (pos W^T).  pos_offsets / pos_logits: one row per QUERY (shared by all N frames,
