@@ -1093,15 +1093,17 @@ def upsample_add(lateral, top, lat_affine=None):
     return out
 
 
-def dwconv3x3_tokens(x, level_shapes, weight, bias, gelu=False):
-    """Depthwise 3x3 convolution (+ bias, + exact GELU) of every pyramid level of a token tensor x (B, N, C) whose levels
-    `level_shapes` = [(h, w), ...] are stored one after the other along N (dvis_dwconv3x3_tokens, one launch per level).
-    weight (C, 1, 3, 3).  fp32 contiguous GPU tensors."""
+def _dwconv3x3_tokens_check(op, x, level_shapes, weight):
     B, N, C = x.shape
     if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and weight.dtype == torch.float32 and C % 4 == 0
             and sum(h * w for h, w in level_shapes) == N and weight.shape == (C, 1, 3, 3)):
-        raise RuntimeError(f"dwconv3x3_tokens: needs a contiguous float32 GPU (B, N, C) tensor, C % 4 == 0, levels summing to N "
+        raise RuntimeError(f"{op}: needs a contiguous float32 GPU (B, N, C) tensor, C % 4 == 0, levels summing to N "
                            f"(x {tuple(x.shape)}, levels {list(level_shapes)})")
+
+
+def _dwconv3x3_tokens_kernel(x, level_shapes, weight, bias, gelu):
+    B, N, C = x.shape
+    _dwconv3x3_tokens_check("dwconv3x3_tokens", x, level_shapes, weight)
     out = torch.empty_like(x)
     wt = weight.detach().reshape(C, 9).contiguous()
     bptr = None if bias is None else native.dev_ptr(bias.detach().contiguous(), "bias")
@@ -1114,6 +1116,70 @@ def dwconv3x3_tokens(x, level_shapes, weight, bias, gelu=False):
             native.check(rc, "dvis_dwconv3x3_tokens")
             off += h * w
     return out
+
+
+def dwconv3x3_tokens_backward(x, level_shapes, weight, bias, grad_out, gelu=False):
+    """Backward of ``dwconv3x3_tokens`` (csrc/dwconv_tokens_backward.hip, one call per level): x the forward's input, grad_out
+    laid out like it -> (grad_x (B, N, C), grad_weight (C, 1, 3, 3), grad_bias (C) or None without a bias).  Exact fp32 without
+    atomics; the levels' weight / bias gradients are added in level order, so every call gives the same bits."""
+    B, N, C = x.shape
+    _dwconv3x3_tokens_check("dwconv3x3_tokens_backward", x, level_shapes, weight)
+    if not (grad_out.is_cuda and grad_out.dtype == torch.float32 and grad_out.shape == x.shape):
+        raise RuntimeError(f"dwconv3x3_tokens_backward: grad_out must be a float32 GPU tensor shaped like x (got {tuple(grad_out.shape)})")
+    grad_out = grad_out.contiguous()
+    dev, lib = x.device, native.lib()
+    wt = weight.detach().reshape(C, 9).contiguous()
+    bptr = None if bias is None else native.dev_ptr(bias.detach().contiguous(), "bias")
+    grad_x = torch.empty_like(x)
+    # per level: grad_weight (C, 9) then grad_bias (C)
+    part = torch.empty((len(level_shapes), 10 * C), dtype=torch.float32, device=dev)
+    nbytes = max(lib.dvis_dwconv3x3_tokens_backward_ws_bytes(B, h, w, C) for h, w in level_shapes)
+    ws = torch.empty((max(nbytes, 16) // 4,), dtype=torch.float32, device=dev)      # shared by the levels (same stream: in order)
+    off = 0
+    with torch.cuda.device(dev):
+        for i, (h, w) in enumerate(level_shapes):
+            base = 4 * off * C
+            rc = lib.dvis_dwconv3x3_tokens_backward(
+                ctypes.c_void_p(x.data_ptr() + base), ctypes.c_void_p(grad_out.data_ptr() + base), native.dev_ptr(wt, "weight"), bptr,
+                int(gelu), N * C, B, h, w, C, ctypes.c_void_p(grad_x.data_ptr() + base), ctypes.c_void_p(part[i].data_ptr()),
+                ctypes.c_void_p(part[i].data_ptr() + 4 * 9 * C) if bias is not None else None, native.dev_ptr(ws, "workspace"),
+                native.stream_ptr(dev))
+            native.check(rc, "dvis_dwconv3x3_tokens_backward")
+            off += h * w
+    total = part[0].clone()
+    for i in range(1, len(level_shapes)):
+        total += part[i]
+    return grad_x, total[:9 * C].reshape(C, 1, 3, 3), (total[9 * C:] if bias is not None else None)
+
+
+class DWConvTokensFunction(Function):
+    """``dwconv3x3_tokens`` under autograd: the forward kernel; nothing but x, weight and bias is saved, the backward
+    recomputes the pre-activation (csrc/dwconv_tokens_backward.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, level_shapes, gelu):
+        ctx.save_for_backward(x, weight, bias)
+        ctx.level_shapes, ctx.gelu = [tuple(s) for s in level_shapes], bool(gelu)
+        return _dwconv3x3_tokens_kernel(x, level_shapes, weight, bias, gelu)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        x, weight, bias = ctx.saved_tensors
+        gx, gw, gb = dwconv3x3_tokens_backward(x, ctx.level_shapes, weight, bias, grad_out, ctx.gelu)
+        need = ctx.needs_input_grad
+        return gx if need[0] else None, gw if need[1] else None, gb if bias is not None and need[2] else None, None, None
+
+
+def dwconv3x3_tokens(x, level_shapes, weight, bias, gelu=False):
+    """Depthwise 3x3 convolution (+ bias, + exact GELU) of every pyramid level of a token tensor x (B, N, C) whose levels
+    `level_shapes` = [(h, w), ...] are stored one after the other along N (dvis_dwconv3x3_tokens, one launch per level).
+    weight (C, 1, 3, 3).  fp32 contiguous GPU tensors.  Differentiable: with grad enabled and an input that requires grad the
+    call goes through DWConvTokensFunction."""
+    if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+        _dwconv3x3_tokens_check("dwconv3x3_tokens", x, level_shapes, weight)
+        return DWConvTokensFunction.apply(x, weight, bias, level_shapes, gelu)
+    return _dwconv3x3_tokens_kernel(x, level_shapes, weight, bias, gelu)
 
 
 def adapter_res2(g, c1, x1_tokens, scale, shift, h8, w8):

@@ -392,14 +392,39 @@ class MinVIS(_VideoBase):
             raise ValueError("MinVIS.train(): every frame of the batch must have one size (the data loader's crop); got "
                              f"{sorted({tuple(f.shape[-2:]) for f in frames})}")
         images, _ = self.preprocess(frames)                 # all frames of all videos: (b t) frames, t = num_frames
-        with Fn.x3_stage("backbone"):
-            features = self.backbone(images)
+        features = self._train_backbone(images)
         outputs = self.sem_seg_head(features)
         targets = self.prepare_targets(batched_inputs, images)
         outputs, targets = self.frame_decoder_loss_reshape(outputs, targets)
         losses = self.criterion(outputs, targets)
         weights = self.criterion.weight_dict
         return {k: v * weights[k] for k, v in losses.items() if k in weights}
+
+    def _train_backbone(self, images):
+        """The backbone's training forward.  A backbone whose frozen part runs on the split-f16 inference kernels under
+        ``no_grad`` (`frozen_part_on_x3`: the ViT-Adapter's ViT) is checked like the frozen segmenter of
+        ``DVIS_Plus_online._forward_train``: range guard behind the call, and on an X3RangeError the call again on the exact kernels
+        (the BatchNorm buffers the first attempt updated are put back first).  Costs one wait for the backbone per step."""
+        if not getattr(self.backbone, "frozen_part_on_x3", False):
+            with Fn.x3_stage("backbone"):
+                return self.backbone(images)
+        saved = [(b, b.detach().clone()) for b in self.backbone.buffers()]
+
+        def run():
+            with self._x3_scope(), Fn.x3_stage("backbone"):
+                features = self.backbone(images)
+            self._guard_verify(self._guard_snapshot())
+            return features
+
+        def again():
+            with torch.no_grad():
+                for b, v in saved:
+                    b.copy_(v)
+            return run()
+        try:
+            return run()
+        except Fn.X3RangeError as e:
+            return self._x3_rerun(e, again)
 
     @staticmethod
     def frame_decoder_loss_reshape(outputs, targets):

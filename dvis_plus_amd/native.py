@@ -79,6 +79,8 @@ SIGNATURES = {
     "dvis_upsample_add_affine": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "dvis_upsample_add": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "dvis_dwconv3x3_tokens": (_i, [_p, _p, _i64, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "dvis_dwconv3x3_tokens_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
+    "dvis_dwconv3x3_tokens_backward": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dvis_adapter_res2": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "dvis_vps_argmax": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "dvis_vss_argmax": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),

@@ -11,8 +11,14 @@ What runs where: the token attention (3681 tokens x 16 heads x d=64 at 720p) is 
 strided views of the fused qkv projection (the reference materialises the (B,16,N,N) probabilities when xformers is
 absent, attention.py:49-61); the extractors call the MSDeformAttn op through its fused single-level path
 (D=64, L=1, P=4); projections / MLPs are library GEMMs; convolutions MIOpen.  LayerScale is folded into the
-projection that precedes it once per weight version (like FrozenBN in backbone.py).  Eval only: drop-path is the
+projection that precedes it once per weight version (like FrozenBN in backbone.py).  Eval: drop-path is the
 identity, SyncBatchNorm is batch-norm with running statistics.
+
+Training (``.train()``, DinoV2ViTAdapter._forward_train — adapter.py:523-583 with FREEZE_VIT: True, FINETUNE: False, what all of
+the reference's vit_adapter yamls set): the ViT runs under ``torch.no_grad()`` on the inference kernels above and gets no
+gradient; the spatial prior module, ``level_embed``, the extractors, ``up`` and ``norm1..4`` are torch ops on live weights
+(BatchNorm with batch statistics), except the extractors' two hot ops, which run on own kernels with own backward kernels:
+``MSDeformAttn.train_forward`` and the ConvFFN's token-major depthwise convolution (``Fn.dwconv3x3_tokens`` under autograd).
 """
 import math
 import os
@@ -198,7 +204,8 @@ class DinoVisionTransformer(nn.Module):
         if npatch == N and w == h:
             return self.pos_embed
         def make():
-            pe = self.pos_embed.detach().float()
+            pe = self.pos_embed.detach()
+            pe = pe if pe.dtype == torch.float64 else pe.float()        # (a float64 module — the training tests' yardstick — stays in float64)
             dim = pe.shape[-1]
             w0, h0 = w // self.patch_size + 0.1, h // self.patch_size + 0.1
             s = int(math.sqrt(N))
@@ -249,10 +256,13 @@ class DWConv(nn.Module):
     def levels(self, N, H, W):
         return [(H * 2, W * 2), (H, W), (H // 2, W // 2)]
 
-    def fused_ok(self, x, H, W):
-        return (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not torch.is_autocast_enabled()
+    def shape_ok(self, x, H, W):
+        return (x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
                 and x.is_contiguous() and x.shape[2] % 4 == 0 and H % 2 == 0 and W % 2 == 0 and x.shape[1] == 21 * (H // 2) * (W // 2)
                 and os.environ.get("DVIS_DWCONV_TOKENS", "1") != "0")
+
+    def fused_ok(self, x, H, W):
+        return not torch.is_grad_enabled() and self.shape_ok(x, H, W)
 
     def forward(self, x, H, W):
         B, N, C = x.shape
@@ -283,6 +293,17 @@ class ConvFFN(nn.Module):
             x = F.gelu(self.dwconv(x, H, W))
         return Fn.linear(x, self.fc2.weight, self.fc2.bias, tall=True, residual=residual)
 
+    def train_forward(self, x, H, W):
+        """adapter.py:73-80 on live weights under autograd (drop = 0 in every config).  Where DWConv.shape_ok holds the depthwise
+        convolution + GELU is the token-major kernel and its backward kernel (csrc/dwconv_tokens_backward.hip); CPU tensors, odd
+        shapes and DVIS_DWCONV_TOKENS=0 take the reference's composition (transposes, grouped Conv2d, GELU, concatenation)."""
+        x = F.linear(x, self.fc1.weight, self.fc1.bias)
+        if self.dwconv.shape_ok(x, H, W):
+            x = Fn.dwconv3x3_tokens(x, self.dwconv.levels(x.shape[1], H, W), self.dwconv.dwconv.weight, self.dwconv.dwconv.bias, gelu=True)
+        else:
+            x = F.gelu(self.dwconv(x, H, W))
+        return F.linear(x, self.fc2.weight, self.fc2.bias)
+
 
 class Extractor(nn.Module):
     def __init__(self, dim, num_heads=6, n_points=4, n_levels=1, deform_ratio=1.0, with_cffn=True, cffn_ratio=0.25):
@@ -308,6 +329,15 @@ class Extractor(nn.Module):
             query = self.ffn(normed, H, W, residual=query)
         return query
 
+    def train_forward(self, query, reference_points, feat, spatial_shapes, level_start_index, H, W):
+        """adapter.py:117-135 on live weights under autograd (drop_path = 0: get_models builds the ViT without stochastic depth)."""
+        ln = lambda norm, t: F.layer_norm(t, norm.normalized_shape, norm.weight, norm.bias, norm.eps)
+        query = query + self.attn.train_forward(ln(self.query_norm, query), reference_points, ln(self.feat_norm, feat), spatial_shapes,
+                                                level_start_index)
+        if self.with_cffn:
+            query = query + self.ffn.train_forward(ln(self.ffn_norm, query), H, W)
+        return query
+
 
 class InteractionBlockWithCls_Efficient(nn.Module):
     """ViT blocks of one stage, then the extractor(s) — adapter.py:262-321 (no injector in this variant)."""
@@ -330,6 +360,20 @@ class InteractionBlockWithCls_Efficient(nn.Module):
         if self.extra_extractors is not None:
             for ex in self.extra_extractors:
                 c = ex(c, ref, x, shapes, lsi, H, W)
+        return x, c, cls
+
+    def train_forward(self, x, c, cls, blocks, deform_inputs2, H, W):
+        """adapter.py:282-302, finetune=False: the ViT blocks under no_grad (on the inference kernels), the extractors under autograd."""
+        with torch.no_grad():
+            x = torch.cat((cls, x), dim=1)
+            for blk in blocks:
+                x = blk(x)
+            cls, x = x[:, :1], x[:, 1:].contiguous()
+        ref, shapes, lsi = deform_inputs2
+        c = self.extractor.train_forward(c, ref, x, shapes, lsi, H, W)
+        if self.extra_extractors is not None:
+            for ex in self.extra_extractors:
+                c = ex.train_forward(c, ref, x, shapes, lsi, H, W)
         return x, c, cls
 
 
@@ -404,11 +448,22 @@ class SpatialPriorModule(nn.Module):
 
 
 class DinoV2ViTAdapter(nn.Module):
+    frozen_part_on_x3 = True      # under .train() the ViT runs under no_grad on the split-f16 inference kernels (MinVIS._train_backbone)
+
     def __init__(self, vit_module=None, pretrain_size=224, conv_inplane=64, n_points=4, deform_num_heads=6,
                  init_values=0.0, interaction_indexes=None, with_cffn=True, cffn_ratio=0.25, deform_ratio=1.0,
                  add_vit_feature=True, use_extra_extractor=True, with_cp=False, freeze_backbone=False, finetune=False,
                  finetune_indexes=(0,)):
+        """freeze_backbone: ``requires_grad_(False)`` on the ViT, as the reference does.  finetune (FINETUNE: True, no yaml of the
+        reference sets it) would train the ViT blocks of `finetune_indexes`: not built, see below.  with_cp: the reference's
+        activation checkpointing of the extractors; accepted, and without effect here — checkpointing trades memory for a second
+        forward and changes no result."""
         super().__init__()
+        if finetune:
+            raise NotImplementedError("dvis_plus_amd: VIT_ADAPTER.FINETUNE needs a backward of the ViT blocks, whose missing piece is a "
+                                      "long-sequence self-attention backward kernel (3681 tokens x 16 heads at 720p); the frozen ViT "
+                                      "(FREEZE_VIT: True, FINETUNE: False, every vit_adapter yaml) trains")
+        self.freeze_backbone, self.finetune, self.finetune_indexes, self.with_cp = bool(freeze_backbone), False, list(finetune_indexes), bool(with_cp)
         self.pretrain_size = (pretrain_size, pretrain_size)
         self.interaction_indexes, self.add_vit_feature = interaction_indexes, add_vit_feature
         dim = vit_module.embed_dim
@@ -428,6 +483,8 @@ class DinoV2ViTAdapter(nn.Module):
                 m._reset_parameters()
         nn.init.normal_(self.level_embed)
         self.vit_module = vit_module
+        if self.freeze_backbone:
+            self.vit_module.requires_grad_(False)
         self._deform_cache = {}
 
     @staticmethod
@@ -458,7 +515,7 @@ class DinoV2ViTAdapter(nn.Module):
     @Fn.fp32_island
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("dvis_plus_amd implements the backbone's inference path")
+            return self._forward_train(x)
         x = Fn.f32(x)
         bs, _, h, w = x.shape
         d2 = self._deform_inputs(h, w, x.device)
@@ -516,6 +573,39 @@ class DinoV2ViTAdapter(nn.Module):
             c4 = c4 + F.interpolate(x4, scale_factor=0.5, mode="bilinear", align_corners=False)
         return [self.norm1(c1) if f1 is None else f1, self.norm2(c2), self.norm3(c3), self.norm4(c4)]
 
+    def _forward_train(self, x):
+        """adapter.py:523-583 under ``.train()`` with finetune=False.  The ViT (token preparation and blocks) runs under
+        ``torch.no_grad()`` on the inference kernels (row images, split-f16 qkv attention) whatever ``self.training`` says and gets
+        no gradient; everything else is autograd on live weights: the spatial prior module and norm1..4 with BatchNorm in training
+        mode (batch statistics; running statistics and num_batches_tracked updated as nn.SyncBatchNorm does on one process), the
+        extractors through ``Extractor.train_forward``, ``up`` / the three interpolations / the additions as torch ops."""
+        x = x if x.dtype == torch.float64 else Fn.f32(x)                # (float64: the tests' yardstick module keeps its dtype)
+        bs, _, h, w = x.shape
+        d2 = self._deform_inputs(h, w, x.device)
+        c1, c2, c3, c4 = self.spm(x)
+        n2, n3 = c2.shape[1], c3.shape[1]
+        c = torch.cat([c2 + self.level_embed[0], c3 + self.level_embed[1], c4 + self.level_embed[2]], dim=1)
+        with torch.no_grad():
+            t, H, W = self.vit_module.prepare_tokens_with_masks(x, masks=None, return_HW=True)
+        dim = t.shape[-1]
+        cls, t = t[:, :1], t[:, 1:]
+        outs = []
+        for i, layer in enumerate(self.interactions):
+            lo, hi = self.interaction_indexes[i]
+            t, c, cls = layer.train_forward(t, c, cls, self.vit_module.blocks[lo:hi + 1], d2, H, W)
+            outs.append(t.transpose(1, 2).reshape(bs, dim, H, W))
+        c2 = c[:, :n2].transpose(1, 2).reshape(bs, dim, H * 2, W * 2)
+        c3 = c[:, n2:n2 + n3].transpose(1, 2).reshape(bs, dim, H, W)
+        c4 = c[:, n2 + n3:].transpose(1, 2).reshape(bs, dim, H // 2, W // 2)
+        c1 = self.up(c2) + c1
+        if self.add_vit_feature:
+            x1, x2, x3, x4 = outs
+            c1 = c1 + F.interpolate(x1, scale_factor=4, mode="bilinear", align_corners=False)
+            c2 = c2 + F.interpolate(x2, scale_factor=2, mode="bilinear", align_corners=False)
+            c3 = c3 + x3
+            c4 = c4 + F.interpolate(x4, scale_factor=0.5, mode="bilinear", align_corners=False)
+        return [self.norm1(c1), self.norm2(c2), self.norm3(c3), self.norm4(c4)]
+
     def _tail_fused_ok(self, c, H, W):
         bns = (self.norm2, self.norm3, self.norm4)
         return (c.is_cuda and c.dtype == torch.float32 and not torch.is_grad_enabled() and H % 2 == 0 and W % 2 == 0
@@ -567,13 +657,18 @@ def get_adapter_args(name="vitl"):
 @BACKBONE_REGISTRY.register()
 class D2VitAdapterDinoV2(DinoV2ViTAdapter):
     """detectron2 backbone surface: forward -> {res2..res5}, output_shape(), size_divisibility (adapter.py:589-651).
-    Built like the reference's, ``D2VitAdapterDinoV2(cfg, input_shape)`` (size from cfg.MODEL.VIT_ADAPTER.NAME; the
-    weight-file / freezing / checkpointing keys are training-time settings), or directly by size name."""
+    Built like the reference's, ``D2VitAdapterDinoV2(cfg, input_shape)`` (cfg.MODEL.VIT_ADAPTER: NAME the size, FREEZE_VIT /
+    FINETUNE / FINETUNE_INDEXES / WITH_CP the constructor's training settings; the weights come through the state dict, not
+    VIT_WEIGHT), or directly by size name."""
 
     def __init__(self, name="vitl", input_shape=None, **overrides):
+        args = {}
         if not isinstance(name, str):                       # a config node
-            name = name.MODEL.VIT_ADAPTER.NAME
-        args = get_adapter_args(name)
+            va = name.MODEL.VIT_ADAPTER
+            name = va.NAME
+            args = dict(freeze_backbone=bool(va.get("FREEZE_VIT", False)), finetune=bool(va.get("FINETUNE", False)),
+                        finetune_indexes=list(va.get("FINETUNE_INDEXES", [0])), with_cp=bool(va.get("WITH_CP", False)))
+        args = {**get_adapter_args(name), **args}
         args.update(overrides)
         super().__init__(**args)
         self._out_features = ["res2", "res3", "res4", "res5"]

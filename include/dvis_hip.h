@@ -513,6 +513,24 @@ int dvis_dwconv3x3_tokens(const float *x, float *out, int64_t batch_stride, int 
                           const float *bias, int gelu, void *stream);
 
 /*
+ * Backward of dvis_dwconv3x3_tokens for one level (csrc/dwconv_tokens_backward.hip).  Replaces what autograd records for the
+ * reference's ConvFFN / DWConv (mask2former/modeling/backbones_vitAdapter/adapter.py:61-98): per level a transposed contiguous copy,
+ * a grouped Conv2d's data and weight gradients, GeluBackward, the transpose back and the concatenation's split.
+ *   x: the forward's input (nothing else is saved); grad_out / grad_x: laid out like x (token (b, y, x) at base + b * batch_stride +
+ *   (y * w + x) * C); weight (C, 1, 3, 3) = C x 9; bias C or NULL; gelu: the forward's flag.  z = conv(x) + bias is recomputed in the
+ *   forward's tap order, dz = grad_out * gelu'(z) (exact erf form), grad_x = conv(dz, flipped taps), grad_weight (C, 9) and grad_bias (C,
+ *   may be NULL) = sums over every token of dz * x-window and dz.
+ * Exact fp32, no atomics: the weight / bias sums go through a bounded number of per-workgroup partial rows added in a fixed order, so
+ * two calls give the same bits.  ws: dvis_dwconv3x3_tokens_backward_ws_bytes(B, h, w, C) bytes (dz + the partial rows; -1 for bad
+ * sizes), 16-byte aligned.  Refused: C % 4 != 0, a batch stride that is not a multiple of 4 floats or < h * w * C, pointers not
+ * 16-byte aligned, null pointers, grad_x aliasing grad_out or x.
+ */
+int64_t dvis_dwconv3x3_tokens_backward_ws_bytes(int B, int h, int w, int C);
+int dvis_dwconv3x3_tokens_backward(const float *x, const float *grad_out, const float *weight, const float *bias, int gelu,
+                                   int64_t batch_stride, int B, int h, int w, int C, float *grad_x, float *grad_weight, float *grad_bias,
+                                   void *ws, void *stream);
+
+/*
  * The stride-4 output of the ViT-Adapter backbone (mask2former/modeling/backbones_vitAdapter/adapter.py, forward:
  * `c1 = self.up(c2) + c1; c1 = c1 + F.interpolate(x1, scale_factor=4, mode="bilinear", align_corners=False); f1 = self.norm1(c1)`).
  * `up` = ConvTranspose2d(C, C, 2, 2) is a GEMM over the stride-8 tokens with 4 C output features ordered (dy, dx, co); the caller
