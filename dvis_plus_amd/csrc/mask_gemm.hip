@@ -51,12 +51,15 @@ constexpr unsigned kOOB = 0x80000000u;
 template <int QT> constexpr size_t lds_bytes() { return (size_t)4 * QT * 16 * kARow * sizeof(float) + QT * 16 * sizeof(int); }
 
 // MODE 0: VEC = rows of `feat` and of the output are 16-byte aligned (HW % 4 == 0 and aligned bases) -> b128 loads/stores.
-// FULLC = C == 4 * CQ (C a multiple of 32, the production 256): no per-channel validity selects in the loop.
+// FULLC = C == 4 * CQ (C a multiple of 32, the production 256): no per-channel validity selects in the loop, and `embed` is read as
+// 16-byte vectors (the host selects it only for a 16-byte aligned `embed`).
 template <int MODE, int QT, bool VEC, bool FULLC>
 __global__ __launch_bounds__(512) void mask_gemm_kernel(
-    const float *__restrict__ embed, const float *__restrict__ feat, int Q, int qbeg, int C, int CQ, int H, int W, int h,
-    int w, int sfac, int gpf, int spf, int total_steps, float *__restrict__ out_logits, uint8_t *__restrict__ out_mask,
+    const float *__restrict__ embed, const float *__restrict__ feat, int Q, int qbeg, int qend, int C, int CQ, int H, int W,
+    int h, int w, int sfac, int gpf, int spf, int total_steps, float *__restrict__ out_logits, uint8_t *__restrict__ out_mask,
     int *__restrict__ allowed_count) {
+  // The pass owns the queries [qbeg, qend), qend <= Q.  Its QT tiles may reach past qend (5 tiles run on the 7-tile form): those
+  // rows belong to the next pass, so they are neither loaded, stored nor counted here.
   extern __shared__ float lds[];   // A: [4 lane groups][QT * 16 queries][kARow]
   constexpr int ROWS = QT * 16;
 
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
   auto flush_counts = [&]() {   // between two barriers
     if (MODE != 0 && cur_b >= 0 && tid < ROWS) {
       const int q = qbeg + tid, c = counts[tid];
-      if (q < Q && c > 0) atomicAdd(&allowed_count[(size_t)cur_b * Q + q], c);
+      if (q < qend && c > 0) atomicAdd(&allowed_count[(size_t)cur_b * Q + q], c);
       counts[tid] = 0;
     }
   };
@@ -145,9 +148,9 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
           const int u4 = idx % n4, rest = idx / n4;
           const int row = rest % ROWS, gg = rest / ROWS;
           const int q = qbeg + row, c = gg * CQ + u4 * 4;
-          const float *erow = embed + ((size_t)b * Q + (q < Q ? q : 0)) * C;
+          const float *erow = embed + ((size_t)b * Q + (q < qend ? q : 0)) * C;
           dst[k] = idx < total4 ? (gg * ROWS + row) * kARow + u4 * 4 : -1;
-          const bool live = idx < total4 && q < Q;
+          const bool live = idx < total4 && q < qend;
           if (FULLC) {
             v[k] = live ? *reinterpret_cast<const dvis_f4 *>(erow + c) : dvis_f4{0.f, 0.f, 0.f, 0.f};
           } else {
@@ -227,7 +230,7 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const unsigned so = (unsigned)(qt * 16 + r) * chan_bytes;   // uniform
-          if (qbeg + qt * 16 + g * 4 + r >= Q) continue;
+          if (qbeg + qt * 16 + g * 4 + r >= qend) continue;
           if (VEC) {
             const dvis_f4 v = dvis_f4{acc[qt][0][r], acc[qt][1][r], acc[qt][2][r], acc[qt][3][r]};
             // (row offset in the VECTOR offset: with an SGPR offset LLVM does not pad a VALU write to the data registers
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
             n_allowed += __popc((unsigned)((bal >> (16 * g)) & 0xffffull));
           }
           if (j == 0 && n_allowed > 0) atomicAdd(&counts[qt * 16 + g * 4 + r], n_allowed);   // LDS
-          if (qbeg + qt * 16 + g * 4 + r >= Q) continue;
+          if (qbeg + qt * 16 + g * 4 + r >= qend) continue;
           const unsigned so = (unsigned)((size_t)(qt * 16 + r) * HW);   // uniform
           if (VEC) {
             if (okc[0]) __builtin_amdgcn_raw_buffer_store_b32(packed, ro, vo, so, 0);
@@ -281,7 +284,7 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
           const unsigned long long bal = __ballot(okc[0] && !blocked);
           const int n_allowed = __popc((unsigned)((bal >> (16 * g)) & 0xffffull));
           if (j == 0 && n_allowed > 0) atomicAdd(&counts[qt * 16 + g * 4 + r], n_allowed);   // LDS
-          if (okc[0] && qbeg + qt * 16 + g * 4 + r < Q)
+          if (okc[0] && qbeg + qt * 16 + g * 4 + r < qend)
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(blocked ? 1 : 0), ro, vo, (unsigned)((qt * 16 + r) * OHW), 0);
         }
     }
@@ -290,53 +293,98 @@ __global__ __launch_bounds__(512) void mask_gemm_kernel(
   flush_counts();
 }
 
+// THE dispatch: how a call is cut into passes over the queries and steps over the pixels, and which instantiation serves a pass —
+// the one place that decides it.  launch acts on the result and dvis_mask_gemm_plan reports it, so what a test is told cannot
+// drift from what runs.  Only shapes and the two alignment facts are read.
+//   fullc         C % 32 == 0 and `embed` 16-byte aligned (the FULLC forms read it as 16-byte vectors); otherwise the
+//                 <MODE, QT, false, false> forms, which read it by scalars and serve every C <= 256
+//   vec           16-byte loads of the map / packed stores: MODE 0 and 2, HW % 4 == 0, map and output 16-byte aligned; only with fullc
+//   gpf, spf      wave groups (64 source pixels; MODE 1: 16 outputs) of a frame, steps of 8 groups of a frame
+//   total_steps   B * spf, shared out over min(total_steps, 256 at 7 query tiles, else 512) workgroups (mask_gemm_pass)
+struct MaskGemmPlan {
+  int tiles, passes, per_pass;
+  bool fullc, vec;
+  int gpf, spf, total_steps;
+};
+struct MaskGemmPass {
+  int qbeg, qend, QT, nwg;   // queries [qbeg, qend) on the QT-tile instantiation
+};
+
+// H x W: the map the kernel reads (MODE 0: 1 x HW); h x w: MODE 1's output.  `op` names the caller in a refusal.
+int mask_gemm_decide(const char *op, int mode, int B, int Q, int C, int H, int W, int h, int w, bool aligned, bool embed_aligned,
+                     MaskGemmPlan *plan) {
+  DVIS_REQUIRE(B >= 0 && Q > 0 && C > 0 && H > 0 && W > 0 && (mode != 1 || (h > 0 && w > 0)), "%s: bad sizes", op);
+  DVIS_REQUIRE(C <= 256, "%s: supports C <= 256 (got C=%d)", op, C);
+  if (mode == 1)
+    DVIS_REQUIRE(H % h == 0 && W % w == 0 && H / h == W / w && (H / h) % 2 == 0,
+                 "%s: needs an even integer down-sizing factor (H=%d W=%d -> h=%d w=%d)", op, H, W, h, w);
+  MaskGemmPlan p;
+  p.tiles = (Q + 15) / 16;
+  p.passes = (p.tiles + kMaxQT - 1) / kMaxQT;
+  p.per_pass = (p.tiles + p.passes - 1) / p.passes;   // 200 queries: 13 tiles -> 7 + 6
+  p.fullc = C % 32 == 0 && embed_aligned;
+  const long long npx = mode == 1 ? (long long)h * w : (long long)H * W;
+  p.vec = p.fullc && mode != 1 && npx % 4 == 0 && aligned;
+  const int per = mode == 1 ? 16 : 64;
+  p.gpf = (int)((npx + per - 1) / per);
+  p.spf = (p.gpf + 7) / 8;
+  const long long total = (long long)B * p.spf;
+  DVIS_REQUIRE(total < (1ll << 31), "%s: too many steps (B=%d)", op, B);
+  p.total_steps = (int)total;
+  *plan = p;
+  return DVIS_OK;
+}
+
+MaskGemmPass mask_gemm_pass(const MaskGemmPlan &plan, int Q, int pass) {
+  const int t0 = pass * plan.per_pass;
+  const int nt = plan.tiles - t0 < plan.per_pass ? plan.tiles - t0 : plan.per_pass;
+  const int QT = nt <= 2 ? 2 : nt <= 4 ? 4 : kMaxQT;
+  // one workgroup per CU at QT = 7 (LDS, 2 waves per SIMD); the small forms fit two
+  const int cap = QT == kMaxQT ? 256 : 512;
+  const int qend = (t0 + nt) * 16 < Q ? (t0 + nt) * 16 : Q;
+  return MaskGemmPass{t0 * 16, qend, QT, plan.total_steps < cap ? plan.total_steps : cap};
+}
+
 template <int MODE, int QT, bool VEC, bool FULLC>
-int launch_one(const float *embed, const float *feat, int B, int Q, int qbeg, int C, int H, int W, int h, int w,
-               float *out_logits, uint8_t *out_mask, int *allowed, hipStream_t st) {
+int launch_one(const float *embed, const float *feat, int Q, int C, int H, int W, int h, int w, const MaskGemmPlan &plan,
+               const MaskGemmPass &pass, float *out_logits, uint8_t *out_mask, int *allowed, hipStream_t st) {
   static DvisLdsOptIn opted;   // per kernel instantiation, per device
   if (const int rc = dvis_lds_opt_in(reinterpret_cast<const void *>(&mask_gemm_kernel<MODE, QT, VEC, FULLC>),
                                      lds_bytes<QT>(), &opted, "mask_gemm"))
     return rc;
   const int CQ = ((C + 3) / 4 + 7) / 8 * 8;
   const int sfac = MODE == 1 ? H / h : 1;
-  const long long npx = MODE == 1 ? (long long)h * w : (long long)H * W;
-  const int per = MODE == 1 ? 16 : 64;
-  const int gpf = (int)((npx + per - 1) / per);
-  const int spf = (gpf + 7) / 8;
-  const long long total = (long long)B * spf;
-  // one workgroup per CU at QT = 7 (LDS, 2 waves per SIMD); the small forms fit two
-  const int nwg = (int)(total < (QT == kMaxQT ? 256 : 512) ? total : (QT == kMaxQT ? 256 : 512));
-  hipLaunchKernelGGL((mask_gemm_kernel<MODE, QT, VEC, FULLC>), dim3(nwg), dim3(512), lds_bytes<QT>(), st, embed, feat, Q, qbeg, C,
-                     CQ, H, W, h, w, sfac, gpf, spf, (int)total, out_logits, out_mask, allowed);
+  hipLaunchKernelGGL((mask_gemm_kernel<MODE, QT, VEC, FULLC>), dim3(pass.nwg), dim3(512), lds_bytes<QT>(), st, embed, feat, Q,
+                     pass.qbeg, pass.qend, C, CQ, H, W, h, w, sfac, plan.gpf, plan.spf, plan.total_steps, out_logits, out_mask, allowed);
   return DVIS_OK;
 }
 
-template <int MODE, bool VEC>
-int launch(const float *embed, const float *feat, int B, int Q, int C, int H, int W, int h, int w, float *out_logits,
-           uint8_t *out_mask, int *allowed, hipStream_t st) {
-  const int tiles = (Q + 15) / 16;
-  const int passes = (tiles + kMaxQT - 1) / kMaxQT;
-  const int per_pass = (tiles + passes - 1) / passes;   // 200 queries: 13 tiles -> 7 + 6
-  for (int pass = 0, t0 = 0; pass < passes; ++pass, t0 += per_pass) {
-    const int nt = tiles - t0 < per_pass ? tiles - t0 : per_pass;
-    const int qbeg = t0 * 16;
+template <int MODE>
+int launch(const float *embed, const float *feat, int Q, int C, int H, int W, int h, int w, const MaskGemmPlan &plan,
+           float *out_logits, uint8_t *out_mask, int *allowed, hipStream_t st) {
+  for (int i = 0; i < plan.passes; ++i) {
+    const MaskGemmPass pass = mask_gemm_pass(plan, Q, i);
     int rc;
-#define DVIS_MG(QT_)                                                                                              \
-  (C % 32 == 0 ? launch_one<MODE, QT_, VEC, true>(embed, feat, B, Q, qbeg, C, H, W, h, w, out_logits, out_mask,  \
-                                                   allowed, st)                                                   \
-               : launch_one<MODE, QT_, false, false>(embed, feat, B, Q, qbeg, C, H, W, h, w, out_logits, out_mask, \
-                                                     allowed, st))
-    if (nt <= 2)
+    // (MODE 1 has no VEC form, and a VEC form exists only with FULLC: the plan never asks for either)
+#define DVIS_MG_ARGS embed, feat, Q, C, H, W, h, w, plan, pass, out_logits, out_mask, allowed, st
+#define DVIS_MG(QT_)                                                                    \
+  (!plan.fullc ? launch_one<MODE, QT_, false, false>(DVIS_MG_ARGS)                      \
+   : plan.vec  ? launch_one<MODE, QT_, MODE != 1, true>(DVIS_MG_ARGS)                   \
+               : launch_one<MODE, QT_, false, true>(DVIS_MG_ARGS))
+    if (pass.QT == 2)
       rc = DVIS_MG(2);
-    else if (nt <= 4)
+    else if (pass.QT == 4)
       rc = DVIS_MG(4);
     else
       rc = DVIS_MG(7);
 #undef DVIS_MG
+#undef DVIS_MG_ARGS
     if (rc != DVIS_OK) return rc;
   }
   return dvis_check_launch("mask_gemm_kernel");
 }
+
+bool aligned16(const void *a, const void *b = nullptr) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
 
 // The four centre pixels of every s x s block of a map, s = 2, 4, 8, averaged in the reference's order ((a + b) + (c + d)) * 0.25
 // — what F.interpolate(bilinear, align_corners=False) by an even integer factor samples — for all three decoder levels in ONE
@@ -394,14 +442,14 @@ DVIS_EXPORT int dvis_attn_mask_pooled(const float *embed, const float *pooled, i
   DVIS_REQUIRE(B >= 0 && Q > 0 && C > 0 && h > 0 && w > 0, "attn_mask_pooled: bad sizes");
   if (B == 0) return DVIS_OK;
   DVIS_REQUIRE(embed && pooled && mask && allowed_count, "attn_mask_pooled: null pointer");
-  DVIS_REQUIRE(C <= 256, "attn_mask_pooled: supports C <= 256 (got C=%d)", C);
+  MaskGemmPlan plan;
+  if (const int rc = mask_gemm_decide("attn_mask_pooled", 2, B, Q, C, h, w, h, w, aligned16(pooled, mask), aligned16(embed), &plan))
+    return rc;
   const int64_t HW = (int64_t)h * w;
   DVIS_REQUIRE((long long)((C + 31) / 32 * 32) * HW * 4 < (1ll << 31) && (long long)Q * HW < (1ll << 31),
                "attn_mask_pooled: one frame of the pooled map / of the mask must stay below 2 GiB");
   if (const int rc = dvis_zero_words(allowed_count, (size_t)B * Q, (hipStream_t)stream, "attn_mask_pooled: zero counts")) return rc;
-  const bool vec = HW % 4 == 0 && (((uintptr_t)pooled | (uintptr_t)mask) & 15) == 0;
-  return vec ? launch<2, true>(embed, pooled, B, Q, C, h, w, h, w, nullptr, mask, allowed_count, (hipStream_t)stream)
-             : launch<2, false>(embed, pooled, B, Q, C, h, w, h, w, nullptr, mask, allowed_count, (hipStream_t)stream);
+  return launch<2>(embed, pooled, Q, C, h, w, h, w, plan, nullptr, mask, allowed_count, (hipStream_t)stream);
 }
 
 DVIS_EXPORT int dvis_mask_logits(const float *embed, const float *feat, int B, int Q, int C, int64_t HW, float *out,
@@ -409,13 +457,13 @@ DVIS_EXPORT int dvis_mask_logits(const float *embed, const float *feat, int B, i
   DVIS_REQUIRE(B >= 0 && Q > 0 && C > 0 && HW > 0, "mask_logits: bad sizes");
   if (B == 0) return DVIS_OK;
   DVIS_REQUIRE(embed && feat && out, "mask_logits: null pointer");
-  DVIS_REQUIRE(C <= 256, "mask_logits: supports C <= 256 (got C=%d)", C);
   DVIS_REQUIRE(HW < (1ll << 31) && (long long)Q * HW * 4 < 0xFFFFFF00ll, "mask_logits: one frame of logits must stay below 4 GiB");
+  MaskGemmPlan plan;
+  if (const int rc = mask_gemm_decide("mask_logits", 0, B, Q, C, 1, (int)HW, 0, 0, aligned16(feat, out), aligned16(embed), &plan))
+    return rc;
   DVIS_REQUIRE((long long)((C + 31) / 32 * 32) * HW * 4 < (1ll << 31),
                "mask_logits: one frame of mask_features must stay below 2 GiB");
-  const bool vec = HW % 4 == 0 && ((uintptr_t)feat | (uintptr_t)out) % 16 == 0;
-  return vec ? launch<0, true>(embed, feat, B, Q, C, 1, (int)HW, 0, 0, out, nullptr, nullptr, (hipStream_t)stream)
-             : launch<0, false>(embed, feat, B, Q, C, 1, (int)HW, 0, 0, out, nullptr, nullptr, (hipStream_t)stream);
+  return launch<0>(embed, feat, Q, C, 1, (int)HW, 0, 0, plan, out, nullptr, nullptr, (hipStream_t)stream);
 }
 
 DVIS_EXPORT int dvis_attn_mask(const float *embed, const float *feat, int B, int Q, int C, int H, int W, int h, int w,
@@ -423,11 +471,28 @@ DVIS_EXPORT int dvis_attn_mask(const float *embed, const float *feat, int B, int
   DVIS_REQUIRE(B >= 0 && Q > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0, "attn_mask: bad sizes");
   if (B == 0) return DVIS_OK;
   DVIS_REQUIRE(embed && feat && mask && allowed_count, "attn_mask: null pointer");
-  DVIS_REQUIRE(C <= 256, "attn_mask: supports C <= 256 (got C=%d)", C);
-  DVIS_REQUIRE(H % h == 0 && W % w == 0 && H / h == W / w && (H / h) % 2 == 0,
-               "attn_mask: needs an even integer down-sizing factor (H=%d W=%d -> h=%d w=%d)", H, W, h, w);
+  MaskGemmPlan plan;
+  if (const int rc = mask_gemm_decide("attn_mask", 1, B, Q, C, H, W, h, w, false, aligned16(embed), &plan)) return rc;
   DVIS_REQUIRE((long long)((C + 31) / 32 * 32) * H * W * 4 < (1ll << 31),
                "attn_mask: one frame of mask_features must stay below 2 GiB");
   if (const int rc = dvis_zero_words(allowed_count, (size_t)B * Q, (hipStream_t)stream, "attn_mask: zero counts")) return rc;
-  return launch<1, false>(embed, feat, B, Q, C, H, W, h, w, nullptr, mask, allowed_count, (hipStream_t)stream);
+  return launch<1>(embed, feat, Q, C, H, W, h, w, plan, nullptr, mask, allowed_count, (hipStream_t)stream);
+}
+
+DVIS_EXPORT int dvis_mask_gemm_plan(int mode, int B, int Q, int C, int H, int W, int h, int w, int aligned, int embed_aligned,
+                                    int32_t *plan, int capacity) {
+  DVIS_REQUIRE(plan != nullptr && capacity >= 0, "mask_gemm_plan: null pointer");
+  DVIS_REQUIRE(mode >= 0 && mode <= 2, "mask_gemm_plan: mode is 0 (mask_logits), 1 (attn_mask) or 2 (attn_mask_pooled)");
+  DVIS_REQUIRE(H > 0 && W > 0 && (long long)H * W < (1ll << 31), "mask_gemm_plan: bad sizes");
+  MaskGemmPlan p;
+  const int rows = mode == 0 ? 1 : H, cols = mode == 0 ? H * W : W;   // dvis_mask_logits takes the map as 1 x HW
+  if (const int rc = mask_gemm_decide("mask_gemm_plan", mode, B, Q, C, rows, cols, h, w, aligned != 0, embed_aligned != 0, &p))
+    return rc;
+  plan[0] = p.passes;
+  for (int i = 0; i < p.passes && i < capacity; ++i) {
+    const MaskGemmPass pass = mask_gemm_pass(p, Q, i);
+    int32_t *o = plan + 1 + 8 * i;
+    o[0] = pass.qbeg, o[1] = pass.QT, o[2] = p.fullc, o[3] = p.vec, o[4] = p.gpf, o[5] = p.spf, o[6] = p.total_steps, o[7] = pass.nwg;
+  }
+  return DVIS_OK;
 }

@@ -597,6 +597,28 @@ def attn_mask_pooled(mask_embed, pooled):
     return mask, allowed
 
 
+MaskGemmPass = collections.namedtuple("MaskGemmPass", "qbeg QT fullc vec gpf spf total_steps nwg")
+
+
+def mask_gemm_plan(mode, B, Q, C, H, W, h=0, w=0, aligned=True, embed_aligned=True):
+    """How csrc/mask_gemm.hip would run ``mask_logits`` (mode 0, map H x W), ``attn_mask`` (mode 1, H x W -> h x w) or
+    ``attn_mask_pooled`` (mode 2, pooled map H x W; h, w unused), without launching it: one MaskGemmPass per pass over the queries —
+    qbeg (its first query), QT (query tiles of the kernel instantiation: 2, 4 or 7), fullc (no per-channel selects and 16-byte
+    reads of mask_embed: C % 32 == 0 and ``embed_aligned``), vec (16-byte map loads and packed stores: modes 0 and 2, H W % 4 == 0,
+    ``aligned``, fullc), gpf / spf (wave groups and steps of 8 groups per frame), total_steps (B * spf) and nwg (the workgroups
+    that share the steps out).  ``aligned``: the map and the output start on 16 bytes; ``embed_aligned``: so does mask_embed.  The
+    answer comes from dvis_mask_gemm_plan, the function the launch itself consults; only shapes are read, so no GPU is needed."""
+    cap = 8
+    while True:
+        buf = (ctypes.c_int32 * (1 + 8 * cap))()
+        rc = native.lib().dvis_mask_gemm_plan(mode, B, Q, C, H, W, h, w, int(aligned), int(embed_aligned), buf, cap)
+        native.check(rc, "dvis_mask_gemm_plan")
+        if buf[0] <= cap:
+            words = [buf[1 + 8 * i:9 + 8 * i] for i in range(buf[0])]
+            return tuple(MaskGemmPass(p[0], p[1], bool(p[2]), bool(p[3]), *p[4:]) for p in words)
+        cap = buf[0]
+
+
 def _strides3(t, B, C, d):
     """(L, B, C) tensor -> {batch, head, row} strides in floats for the kernel's (B, heads, L, d) view."""
     return (ctypes.c_int64 * 3)(t.stride(1) if B > 1 else C, d, t.stride(0))

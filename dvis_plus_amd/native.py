@@ -44,6 +44,7 @@ SIGNATURES = {
     "dvis_attn_mask": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "dvis_center_pool3": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p]),
     "dvis_attn_mask_pooled": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "dvis_mask_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i]),
     "dvis_attention_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_attention_ws_bytes_k": (_i64, [_i, _i, _i, _i, _i]),
     "dvis_attention_plan": (_i, [_i, _i, _i, _i, _i, _i64, _i64, _i, _p]),

@@ -266,6 +266,16 @@ int dvis_attn_mask(const float *embed, const float *feat, int B, int Q, int C, i
 int dvis_center_pool3(const float *feat, int64_t planes, int H, int W, float *p2, float *p4, float *p8, void *stream);
 int dvis_attn_mask_pooled(const float *embed, const float *pooled, int B, int Q, int C, int h, int w, uint8_t *mask,
                           int32_t *allowed_count, void *stream);
+/* How dvis_mask_logits (mode 0, map H x W), dvis_attn_mask (mode 1, H x W -> h x w) or dvis_attn_mask_pooled (mode 2, pooled map
+ * H x W; h, w unused) would run, from the function their launch consults (host only, launches nothing).  aligned: the map and the
+ * output are 16-byte aligned; embed_aligned: so is `embed`.  plan[0] = number of passes over the queries (of at most 112), then for
+ * each of the first min(passes, capacity) passes 8 words: qbeg (its first query), QT (query tiles of the instantiation: 2, 4 or 7),
+ * fullc (C % 32 == 0 and embed aligned: 16-byte reads of embed, no per-channel selects), vec (16-byte map loads and packed stores:
+ * modes 0 and 2, HW % 4 == 0, aligned, fullc), gpf (wave groups per frame: of 64 map pixels, mode 1 of 16 outputs), spf (steps of 8
+ * groups per frame), total_steps (B * spf) and nwg (workgroups that share the steps out: min(total_steps, 256 at QT = 7, else 512)).
+ * plan holds 1 + 8 * capacity words.  Refuses the shapes the three entry points refuse (C > 256, mode 1 without an even factor). */
+int dvis_mask_gemm_plan(int mode, int B, int Q, int C, int H, int W, int h, int w, int aligned, int embed_aligned, int32_t *plan,
+                        int capacity);
 
 /*
  * softmax(Q K^T * scale [masked]) V for B batch entries x `heads` heads, fp32 in/out, exact-fp32 MFMA.
