@@ -319,16 +319,43 @@ class _VideoBase(nn.Module):
             Fn.X3_GUARD.verify_gathered(shard.last_guard_tags, self.device, self)
         return out
 
-    def _x3_rerun(self, err, run):
+    def _x3_rerun(self, err, run, stacklevel=3):
         """X3RangeError policy of a single-GPU call: re-run `run()` on the exact-fp32 kernels (and stay on them), or raise."""
         sharded = self.clip_shard.world > 1 or self.clip_shard.force
         if sharded or Fn.X3_ON_OVERFLOW != "rerun":
             raise err
         import warnings
         warnings.warn(f"{err}  Re-running the clip on the exact-fp32 kernels; this model stays on them (DVIS_X3_ON_OVERFLOW=raise "
-                      "turns this into an error).", RuntimeWarning, stacklevel=3)
+                      "turns this into an error).", RuntimeWarning, stacklevel=stacklevel)
         self._x3_off = True
         return run()
+
+    # ---- shared by the training stages
+    def _segment_frozen(self, images):
+        """The frozen segmenter of the tracker / refiner stage (the caller holds no_grad): ``segment`` with the range guard behind
+        it, once more on the exact kernels on an X3RangeError.  -> (embds, embds_nn, logits, mask_features)."""
+        def run():
+            with self._x3_scope():
+                out = self.segment(images)
+            self._guard_verify(self._guard_snapshot())
+            return out
+        try:
+            return run()
+        except Fn.X3RangeError as e:
+            return self._x3_rerun(e, run, stacklevel=4)          # the warning names the caller of _forward_train, as before
+
+    def _weighted(self, losses):
+        weights = self.criterion.weight_dict
+        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+
+    @staticmethod
+    def _per_frame_targets(targets):
+        return [{"labels": t["labels"], "ids": t["ids"][:, [f]], "masks": t["masks"][:, [f]]}
+                for t in targets for f in range(t["ids"].shape[1])]
+
+    @staticmethod
+    def _to_bctq(z):
+        return z.permute(2, 0, 1).unsqueeze(0)                   # (T,Q,C) -> (1,C,T,Q)
 
     def _x3_scope(self):
         """Context for a model call: the exact kernels once a range error was seen (`_x3_off`), else nothing."""
@@ -397,8 +424,7 @@ class MinVIS(_VideoBase):
         targets = self.prepare_targets(batched_inputs, images)
         outputs, targets = self.frame_decoder_loss_reshape(outputs, targets)
         losses = self.criterion(outputs, targets)
-        weights = self.criterion.weight_dict
-        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+        return self._weighted(losses)
 
     def _train_backbone(self, images):
         """The backbone's training forward.  A backbone whose frozen part runs on the split-f16 inference kernels under
@@ -435,9 +461,7 @@ class MinVIS(_VideoBase):
         out = {**outputs, **one(outputs)}
         if "aux_outputs" in outputs:
             out["aux_outputs"] = [one(a) for a in outputs["aux_outputs"]]
-        per_frame = [{"labels": t["labels"], "ids": t["ids"][:, [f]], "masks": t["masks"][:, [f]]}
-                     for t in targets for f in range(t["ids"].shape[1])]
-        return out, per_frame
+        return out, _VideoBase._per_frame_targets(targets)
 
     @Fn.fp32_island
     def _forward_eval(self, batched_inputs):
@@ -512,23 +536,13 @@ class DVIS_Plus_online(_VideoBase):
         pred = self.sem_seg_head.predictor
         with torch.no_grad():
             images, _ = self.preprocess(video["image"])
-
-            def run():
-                with self._x3_scope():
-                    out = self.segment(images)
-                self._guard_verify(self._guard_snapshot())
-                return out
-            try:
-                embds, embds_nn, logits, mask_features = run()
-            except Fn.X3RangeError as e:
-                embds, embds_nn, logits, mask_features = self._x3_rerun(e, run)
+            embds, embds_nn, logits, mask_features = self._segment_frozen(images)
             # the segmenter's own per-frame masks: the matcher's guide during the first half of the schedule
             C = pred.decoder_norm.weight.shape[0]
             image_masks = Fn.mask_logits(pred.mask_embed(embds[..., :C].contiguous()).contiguous(), mask_features)      # (T, Q, h, w)
             object_labels = self._get_instance_labels(logits)
-        to_bctq = lambda z: z.permute(2, 0, 1).unsqueeze(0)
-        outputs, indices = self.tracker(to_bctq(embds), mask_features.unsqueeze(0), return_indices=True, resume=self.keep,
-                                        frame_classes=object_labels, frame_embeds_no_norm=to_bctq(embds_nn))
+        outputs, indices = self.tracker(self._to_bctq(embds), mask_features.unsqueeze(0), return_indices=True, resume=self.keep,
+                                        frame_classes=object_labels, frame_embeds_no_norm=self._to_bctq(embds_nn))
         image_outputs = self.reset_image_output_order({"pred_logits": logits, "pred_masks": image_masks}, indices)
         targets = self.prepare_targets(batched_inputs, images)
         image_outputs, outputs, targets = self.frame_decoder_loss_reshape(outputs, targets, image_outputs)
@@ -537,8 +551,7 @@ class DVIS_Plus_online(_VideoBase):
         if self.use_cl:
             losses.update(reference_contrastive_loss(outputs["pred_references"], match))
         self.iter += 1
-        weights = self.criterion.weight_dict
-        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+        return self._weighted(losses)
 
     @staticmethod
     def _get_instance_labels(pred_logits):
@@ -565,9 +578,7 @@ class DVIS_Plus_online(_VideoBase):
         out["aux_outputs"] = [one(a) for a in outputs.get("aux_outputs", ())]
         if image_outputs is not None:                                                                        # (T, Q, ...) already
             image_outputs = {"pred_masks": image_outputs["pred_masks"].unsqueeze(2), "pred_logits": image_outputs["pred_logits"]}
-        per_frame = [{"labels": t["labels"], "ids": t["ids"][:, [f]], "masks": t["masks"][:, [f]]}
-                     for t in targets for f in range(t["ids"].shape[1])]
-        return image_outputs, out, per_frame
+        return image_outputs, out, _VideoBase._per_frame_targets(targets)
 
     @Fn.fp32_island
     def _forward_eval(self, batched_inputs):
@@ -661,25 +672,15 @@ class DVIS_Plus_offline(_VideoBase):
         self.backbone.eval()
         self.sem_seg_head.eval()
         self.tracker.eval()
-        to_bctq = lambda z: z.permute(2, 0, 1).unsqueeze(0)
         with torch.no_grad():
             images, _ = self.preprocess(video["image"])
-
-            def run():
-                with self._x3_scope():
-                    out = self.segment(images)
-                self._guard_verify(self._guard_snapshot())
-                return out
-            try:
-                embds, embds_nn, logits, mask_features = run()
-            except Fn.X3RangeError as e:
-                embds, embds_nn, logits, mask_features = self._x3_rerun(e, run)
+            embds, embds_nn, logits, mask_features = self._segment_frozen(images)
             mask_features = mask_features.unsqueeze(0)
-            track = self.tracker(to_bctq(embds), mask_features, resume=self.keep, frame_classes=self._get_instance_labels(logits),
-                                 frame_embeds_no_norm=to_bctq(embds_nn))
+            track = self.tracker(self._to_bctq(embds), mask_features, resume=self.keep, frame_embeds_no_norm=self._to_bctq(embds_nn),
+                                 frame_classes=self._get_instance_labels(logits))
             # the tracker's own prediction: the matcher's guide during the first half of the schedule
             image_outputs = {"pred_logits": track["pred_logits"], "pred_masks": track["pred_masks"]}
-            instance_embeds, frame_embeds = track["pred_embds"].clone(), to_bctq(embds_nn).clone()
+            instance_embeds, frame_embeds = track["pred_embds"].clone(), self._to_bctq(embds_nn).clone()
         outputs = self.refiner(instance_embeds, frame_embeds, mask_features)
         targets = self.prepare_targets(batched_inputs, images)
         guide = image_outputs if self.iter < self.max_iter_num // 2 else None
@@ -689,8 +690,7 @@ class DVIS_Plus_offline(_VideoBase):
         if self.use_cl:
             losses.update(refiner_contrastive_loss(outputs["pred_embds"][0].permute(1, 2, 0), match[0], targets[0]["labels"],
                                                    self.classes_references_memory))
-        weights = self.criterion.weight_dict
-        return {k: v * weights[k] for k, v in losses.items() if k in weights}
+        return self._weighted(losses)
 
     @staticmethod
     def frame_decoder_loss_reshape(outputs, targets, image_outputs=None):

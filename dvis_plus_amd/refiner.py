@@ -21,7 +21,8 @@ from torch import nn
 from . import functions as Fn
 from .graphs import ConvAsGemm, FusedKV, GraphRunner
 from .tracker import use_own_gemm
-from .transformer_decoder import MLP, CrossAttentionLayer, FFNLayer, SelfAttentionLayer
+from .transformer_decoder import (MLP, CrossAttentionLayer, FFNLayer, SelfAttentionLayer, layer_mask_logits,
+                                  layer_predictions)
 
 
 class TemporalRefiner(nn.Module):
@@ -131,13 +132,6 @@ class TemporalRefiner(nn.Module):
             return Fn.attention(q, k, v, self.num_heads)
         return Fn.attention(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1), self.num_heads).transpose(0, 1)
 
-    def _train_self_attention(self, layer, x, over_time):
-        C = x.shape[-1]
-        qkv = F.linear(x, layer.self_attn.in_proj_weight, layer.self_attn.in_proj_bias)
-        att = self._train_attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], over_time)
-        op = layer.self_attn.out_proj
-        return layer.norm(x + F.linear(att, op.weight, op.bias))
-
     def _train_short_aggregate(self, i, x):
         """``_short_aggregate`` with F.linear on the weights themselves (no cached re-layout: the gradient must reach them)."""
         T = x.shape[0]
@@ -161,18 +155,15 @@ class TemporalRefiner(nn.Module):
         L = self.num_layers
         x = instance_embeds.permute(2, 0, 3, 1).reshape(T, Q, C)
         fe = frame_embeds.permute(2, 0, 3, 1).reshape(T, Q, C)
+        over_time = lambda q, k, v: self._train_attention(q, k, v, over_time=True)
+        over_queries = lambda q, k, v: self._train_attention(q, k, v, over_time=False)
         layers = []
         for i in range(L):
-            x = self._train_self_attention(self.transformer_time_self_attention_layers[i], x, over_time=True)
+            x = self.transformer_time_self_attention_layers[i].train_forward(x, over_time)
             x = self.conv_norms[i](self._train_short_aggregate(i, x) + x)
-            x = self._train_self_attention(self.transformer_obj_self_attention_layers[i], x, over_time=False)
-            ca = self.transformer_cross_attention_layers[i]
-            W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
-            att = self._train_attention(F.linear(x, W[:C], b[:C]), F.linear(fe, W[C:2 * C], b[C:2 * C]),
-                                        F.linear(fe, W[2 * C:], b[2 * C:]), over_time=False)
-            x = ca.norm(x + F.linear(att, ca.multihead_attn.out_proj.weight, ca.multihead_attn.out_proj.bias))
-            ff = self.transformer_ffn_layers[i]
-            x = ff.norm(x + ff.linear2(torch.relu(ff.linear1(x))))
+            x = self.transformer_obj_self_attention_layers[i].train_forward(x, over_queries)
+            x = self.transformer_cross_attention_layers[i].train_forward(x, x, fe, fe, over_queries)
+            x = self.transformer_ffn_layers[i].train_forward(x)
             layers.append(x)
         dec = self.decoder_norm(torch.stack(layers, dim=0)).unsqueeze(1)          # (l, b, t, q, c)
         # ---- heads on every layer (refiner.py:196-223)
@@ -180,17 +171,8 @@ class TemporalRefiner(nn.Module):
         activation = F.linear(dec, ap.weight, ap.bias).softmax(dim=2)
         pooled = (dec * activation).sum(dim=2, keepdim=True).repeat(1, 1, T, 1, 1)
         outputs_class = F.linear(pooled, ce.weight, ce.bias)                       # (l, b, t, q, K + 1)
-        emb = dec
-        for j, lin in enumerate(self.mask_embed.layers):
-            emb = F.linear(emb, lin.weight, lin.bias)
-            emb = torch.relu(emb) if j < self.mask_embed.num_layers - 1 else emb
-        b_, t_, cm, h, w = mask_features.shape
-        rows = emb[:, 0].permute(1, 0, 2, 3).reshape(T, L * Q, cm)                # a frame's rows: layers x queries
-        logits = Fn.mask_logits(rows, mask_features[0].detach().contiguous())     # (t, l q, h, w)
-        outputs_mask = logits.view(T, L, Q, h, w).permute(1, 2, 0, 3, 4).unsqueeze(1)   # (l, b, q, t, h, w)
-        return {"pred_logits": outputs_class[-1], "pred_masks": outputs_mask[-1],
-                "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(outputs_class[:-1], outputs_mask[:-1])],
-                "pred_embds": dec[-1].permute(0, 3, 1, 2)}
+        outputs_mask = layer_mask_logits(self.mask_embed.train_forward(dec), mask_features, Fn.mask_logits)   # (l, b, q, t, h, w)
+        return {**layer_predictions(outputs_class, outputs_mask), "pred_embds": dec[-1].permute(0, 3, 1, 2)}
 
     def pred_class(self, decoder_output):
         """(l, b, t, q, c): softmax-over-time pooled class logits, repeated T times (refiner.py:196-210)."""

@@ -21,7 +21,6 @@ import random
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from . import cpu_ops
@@ -29,7 +28,8 @@ from . import functions as Fn
 from . import native
 from .graphs import FusedKV, GraphRunner
 from .pixel_decoder import c2_xavier_fill
-from .transformer_decoder import MLP, FFNLayer, SelfAttentionLayer, _xavier_
+from .transformer_decoder import (MLP, CrossAttentionLayer, FFNLayer, SelfAttentionLayer, _xavier_, layer_mask_logits,
+                                  layer_predictions)
 
 
 def use_own_gemm(module):
@@ -72,6 +72,8 @@ class ReferringCrossAttentionLayer(nn.Module):
         W, b = self.multihead_attn.in_proj_weight, self.multihead_attn.in_proj_bias
         return self.attend(indentify, tgt, Fn.linear(key, W[C:2 * C], b[C:2 * C], own=self.own_gemm),
                            Fn.linear(memory, W[2 * C:], b[2 * C:], own=self.own_gemm))
+
+    train_forward = CrossAttentionLayer.train_forward      # (indentify, tgt, key, memory, attend): same parameters, same maths
 
 
 def match_chain(cost):
@@ -328,26 +330,11 @@ class ReferringTracker_noiser(nn.Module):
                 last_outputs = outputs[T - 1]
         return outputs, refs, last_outputs
 
-    def _train_layer(self, j, x, reference, key):
-        """Layer j of the training path as torch ops under autograd: referring cross-attention (query `reference`, keys and
-        values the frame's own queries `key`, residual `x`), self-attention, FFN — post-norm, dropout 0 (tracker.py:293-329)."""
-        C = x.shape[-1]
-        ca, sa, ff = (self.transformer_cross_attention_layers[j], self.transformer_self_attention_layers[j],
-                      self.transformer_ffn_layers[j])
-        W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
-        att = cpu_ops.attention(F.linear(reference, W[:C], b[:C]), F.linear(key, W[C:2 * C], b[C:2 * C]),
-                                F.linear(key, W[2 * C:], b[2 * C:]), ca.nhead)
-        x = ca.norm(x + F.linear(att, ca.multihead_attn.out_proj.weight, ca.multihead_attn.out_proj.bias))
-        qkv = F.linear(x, sa.self_attn.in_proj_weight, sa.self_attn.in_proj_bias)
-        att = cpu_ops.attention(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], sa.nhead)
-        x = sa.norm(x + F.linear(att, sa.self_attn.out_proj.weight, sa.self_attn.out_proj.bias))
-        return ff.norm(x + ff.linear2(torch.relu(ff.linear1(x))))
-
     def _forward_train(self, frame_embeds, mask_features, resume, return_indices, frame_classes, frame_embeds_no_norm):
         """The training forward (tracker.py:187-357): layer by layer, the noiser active from frame 1 on, the outputs of all L
-        layers kept and sent through the heads; aux_outputs holds layers 0 .. L - 2.  The layers' 100 x 256 matrices are torch
-        ops under autograd; the mask logits of all layers and frames — the one heavy tensor with a gradient — are ONE
-        Fn.projected_mask_logits call per clip with layers x queries rows per frame."""
+        layers kept and sent through the heads; aux_outputs holds layers 0 .. L - 2.  A layer is the layer classes' train_forward
+        (tracker.py:293-329) around the torch formulation of attention, on every device; the mask logits of all layers and
+        frames — the one heavy tensor with a gradient — are ONE Fn.projected_mask_logits call per clip (layer_mask_logits)."""
         if self.noiser is None:
             raise ValueError(f"noise_mode {self.noise_mode!r}: the training path needs one of 'none', 'rs', 'wa', 'cc'")
         dt = self.decoder_norm.weight.dtype            # fp32; a module moved to double (tests: the fp64 yardstick) stays there
@@ -360,6 +347,7 @@ class ReferringTracker_noiser(nn.Module):
         assert B == 1, "the tracker trains one video at a time (the noiser matches on batch entry 0, noiser.py:45)"
         outputs, references, ret_indices = [], [], []
         last = self.last_outputs
+        attend = lambda q, k, v: cpu_ops.attention(q, k, v, self.num_heads)
         for i in range(T):
             single, key = fe[i], fe_nn[i]
             classes = None if frame_classes is None else frame_classes[i]
@@ -377,7 +365,9 @@ class ReferringTracker_noiser(nn.Module):
             layers = []
             for j in range(L):
                 # frame 0 of a video: every layer's reference is ref_proj of its own input (the frame's queries for layer 0)
-                x = self._train_layer(j, x, reference if not start else self.ref_proj(key if j == 0 else x), key)
+                ref_j = reference if not start else self.ref_proj(key if j == 0 else x)
+                x = self.transformer_cross_attention_layers[j].train_forward(x, ref_j, key, key, attend)   # residual x, k = v = key
+                x = self.transformer_ffn_layers[j].train_forward(self.transformer_self_attention_layers[j].train_forward(x, attend))
                 layers.append(x)
             self.last_reference = self.ref_proj(key) if start else reference
             references.append(self.last_reference)
@@ -393,19 +383,11 @@ class ReferringTracker_noiser(nn.Module):
         dec = self.decoder_norm(outputs).permute(1, 3, 0, 2, 4)                # (l, b, t, q, c)
         refs = references.unsqueeze(1).expand(T, L, Q, B, C).permute(1, 3, 0, 2, 4)
         outputs_class = self.class_embed(torch.cat([refs, dec], dim=-1))       # (l, b, t, q, K + 1)
-        mask_embed = self.mask_embed(dec)                                      # (l, b, t, q, cm)
-        b_, t_, cm, h, w = mask_features.shape
-        rows = mask_embed[:, 0].permute(1, 0, 2, 3).reshape(T, L * Q, cm)      # a frame's rows: layers x queries
         proj = self.mask_feature_proj
-        logits = Fn.projected_mask_logits(rows, mask_features[0].detach().contiguous(), proj.weight, proj.bias)   # (t, l q, h, w)
-        outputs_mask = logits.view(T, L, Q, h, w).permute(1, 2, 0, 3, 4).unsqueeze(1)   # (l, b, q, t, h, w)
-        out = {
-            "pred_logits": outputs_class[-1],
-            "pred_masks": outputs_mask[-1],
-            "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(outputs_class[:-1], outputs_mask[:-1])],
-            "pred_embds": outputs[:, -1].permute(2, 3, 0, 1),
-            "pred_references": references.permute(2, 3, 0, 1),
-        }
+        outputs_mask = layer_mask_logits(self.mask_embed(dec), mask_features,  # (l, b, q, t, h, w)
+                                         lambda rows, feats: Fn.projected_mask_logits(rows, feats, proj.weight, proj.bias))
+        out = layer_predictions(outputs_class, outputs_mask)
+        out.update(pred_embds=outputs[:, -1].permute(2, 3, 0, 1), pred_references=references.permute(2, 3, 0, 1))
         if return_indices:
             return out, ret_indices
         return out

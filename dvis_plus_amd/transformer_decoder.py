@@ -21,6 +21,7 @@ Inference-only re-organisation for MI355X (same numbers as the reference's eval 
 Under ``.train()`` all four classes run ``_train_layers`` instead: the reference's training forward (L + 1 predictions,
 ``aux_outputs``, the (b t) -> (b, t) split by ``num_frames``) as torch ops under autograd around ``Fn.masked_attention``
 (cross-attention; backward csrc/masked_attention_backward.hip), ``Fn.attention`` (self-attention) and ``Fn.mask_logits``.
+The training maths of a layer is its class's ``train_forward`` — the one spelling the decoders, the tracker and the refiner call.
 """
 import torch
 import torch.nn.functional as F
@@ -66,6 +67,20 @@ class SelfAttentionLayer(nn.Module):
         op = self.self_attn.out_proj
         return Fn.add_layer_norm(Fn.linear(att, op.weight, op.bias, own=own), tgt, self.norm)
 
+    def train_forward(self, tgt, attend, query_pos=None):
+        """``forward`` as torch ops on the live parameters (fused / split projection as there); attend(q, k, v) -> attention."""
+        C = tgt.shape[-1]
+        W, b = self.self_attn.in_proj_weight, self.self_attn.in_proj_bias
+        if query_pos is None:
+            qkv = F.linear(tgt, W, b)
+            q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+        else:
+            qk = F.linear(tgt + query_pos, W[:2 * C], b[:2 * C])
+            q, k = qk[..., :C], qk[..., C:]
+            v = F.linear(tgt, W[2 * C:], b[2 * C:])
+        op = self.self_attn.out_proj
+        return self.norm(tgt + F.linear(attend(q, k, v), op.weight, op.bias))
+
 
 class CrossAttentionLayer(nn.Module):
     own_gemm = None
@@ -104,6 +119,14 @@ class CrossAttentionLayer(nn.Module):
         q_in = tgt if query_pos is None else tgt + query_pos
         return self.attend(tgt, q_in, k, v, memory_mask)
 
+    def train_forward(self, tgt, q_in, k_in, v_in, attend):
+        """Residual `tgt`, un-projected q / k / v inputs: torch ops on the live parameters; attend(q, k, v) -> attention."""
+        C = tgt.shape[-1]
+        W, b = self.multihead_attn.in_proj_weight, self.multihead_attn.in_proj_bias
+        att = attend(F.linear(q_in, W[:C], b[:C]), F.linear(k_in, W[C:2 * C], b[C:2 * C]), F.linear(v_in, W[2 * C:], b[2 * C:]))
+        op = self.multihead_attn.out_proj
+        return self.norm(tgt + F.linear(att, op.weight, op.bias))
+
 
 class FFNLayer(nn.Module):
     own_gemm = None
@@ -121,6 +144,10 @@ class FFNLayer(nn.Module):
         h = Fn.linear_relu(tgt, self.linear1, own=self.own_gemm)
         return Fn.add_layer_norm(Fn.linear(h, self.linear2.weight, self.linear2.bias, own=self.own_gemm), tgt, self.norm)
 
+    def train_forward(self, tgt):
+        h = torch.relu(F.linear(tgt, self.linear1.weight, self.linear1.bias))
+        return self.norm(tgt + F.linear(h, self.linear2.weight, self.linear2.bias))
+
 
 class MLP(nn.Module):
     own_gemm = None
@@ -135,6 +162,28 @@ class MLP(nn.Module):
         for i, layer in enumerate(self.layers):
             x = Fn.linear(x, layer.weight, layer.bias, relu=i < self.num_layers - 1, own=self.own_gemm)
         return x
+
+    def train_forward(self, x):
+        for i, layer in enumerate(self.layers):
+            x = F.linear(x, layer.weight, layer.bias)
+            x = torch.relu(x) if i < self.num_layers - 1 else x
+        return x
+
+
+def layer_predictions(logits, masks):
+    """Per-layer class logits and masks (lists, or tensors with a leading layer dimension): the last is the prediction."""
+    return {"pred_logits": logits[-1], "pred_masks": masks[-1],
+            "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(logits[:-1], masks[:-1])]}
+
+
+def layer_mask_logits(mask_embed, mask_features, mask_logits):
+    """mask_embed (l, b, t, q, cm), mask_features (b, t, cm, h, w) as a constant, b = 1 -> the (l, b, q, t, h, w) view of ONE
+    `mask_logits(rows, features)` call (Fn.mask_logits, or Fn.projected_mask_logits with its weights): a frame's rows are l x q."""
+    L, _, T, Q, cm = mask_embed.shape
+    h, w = mask_features.shape[-2:]
+    rows = mask_embed[:, 0].permute(1, 0, 2, 3).reshape(T, L * Q, cm)
+    logits = mask_logits(rows, mask_features[0].detach().contiguous())          # (t, l q, h, w)
+    return logits.view(T, L, Q, h, w).permute(1, 2, 0, 3, 4).unsqueeze(1)
 
 
 class _MaskedDecoderBase(nn.Module):
@@ -296,15 +345,6 @@ class _MaskedDecoderBase(nn.Module):
 
     # ---- training (video_mask2former_transformer_decoder.py:258-379): torch ops under autograd around the attention kernels --------
 
-    @staticmethod
-    def _train_mlp(mlp, x):
-        if not isinstance(mlp, MLP):
-            return mlp(x)
-        for j, lin in enumerate(mlp.layers):
-            x = F.linear(x, lin.weight, lin.bias)
-            x = torch.relu(x) if j < mlp.num_layers - 1 else x
-        return x
-
     def _train_layers(self, x, mask_features):
         """The training forward of the layers and of the heads on the learnable queries and after every layer.
         x: 3 feature maps (N, C, h_l, w_l), low-res first; mask_features (N, Cm, H, W).  Returns (output (Q, N, C) un-normed after
@@ -317,7 +357,6 @@ class _MaskedDecoderBase(nn.Module):
         reference detaches at :377).  The mask logits of all L + 1 predictions are ONE Fn.mask_logits call with (L + 1) Q rows per
         frame while mask_features needs no gradient, one call per prediction when it does (that gradient contracts over at most
         256 rows, Fn._mask_logits_grad_features).  No graph capture here."""
-        C = self.decoder_norm.weight.shape[0]
         N = x[0].shape[0]
         nh, L = self.num_heads, self.num_layers
         size_list, src, pos = [], [], []
@@ -336,7 +375,7 @@ class _MaskedDecoderBase(nn.Module):
         def heads(output):
             dec = self.decoder_norm(output).transpose(0, 1)                                     # (N, Q, C)
             logits.append(F.linear(dec, self.class_embed.weight, self.class_embed.bias))
-            embs.append(self._train_mlp(self.mask_embed, dec))
+            embs.append(self.mask_embed.train_forward(dec))
             return dec
 
         dec = heads(output)
@@ -346,19 +385,12 @@ class _MaskedDecoderBase(nn.Module):
                 mask, allowed = Fn.attn_mask(embs[-1].detach().contiguous(), feats, size_list[lvl])
             if self.debug_masks is not None:     # rows blocked everywhere attend everywhere (…decoder.py:296)
                 self.debug_masks.append(mask.bool() & (allowed > 0)[..., None])
-            ca = self.transformer_cross_attention_layers[i]
-            W, b = ca.multihead_attn.in_proj_weight, ca.multihead_attn.in_proj_bias
-            att = Fn.masked_attention(F.linear(output + query_embed, W[:C], b[:C]), F.linear(src[lvl] + pos[lvl], W[C:2 * C], b[C:2 * C]),
-                                      F.linear(src[lvl], W[2 * C:], b[2 * C:]), nh, mask, allowed)
-            op = ca.multihead_attn.out_proj
-            output = ca.norm(output + F.linear(att, op.weight, op.bias))
-            sa = self.transformer_self_attention_layers[i]
-            W, b = sa.self_attn.in_proj_weight, sa.self_attn.in_proj_bias
-            qk = F.linear(output + query_embed, W[:2 * C], b[:2 * C])
-            att = Fn.attention(qk[..., :C], qk[..., C:], F.linear(output, W[2 * C:], b[2 * C:]), nh)
-            output = sa.norm(output + F.linear(att, sa.self_attn.out_proj.weight, sa.self_attn.out_proj.bias))
-            ff = self.transformer_ffn_layers[i]
-            output = ff.norm(output + ff.linear2(torch.relu(ff.linear1(output))))
+            output = self.transformer_cross_attention_layers[i].train_forward(
+                output, output + query_embed, src[lvl] + pos[lvl], src[lvl],
+                lambda q, k, v: Fn.masked_attention(q, k, v, nh, mask, allowed))
+            output = self.transformer_self_attention_layers[i].train_forward(
+                output, lambda q, k, v: Fn.attention(q, k, v, nh), query_pos=query_embed)
+            output = self.transformer_ffn_layers[i].train_forward(output)
             dec = heads(output)
         Q = output.shape[0]
         if mask_features.requires_grad and torch.is_grad_enabled():
@@ -376,10 +408,12 @@ class _MaskedDecoderBase(nn.Module):
     @staticmethod
     def _train_video_outputs(b, t, logits, masks):
         """'(b t) q c -> b t q c' and '(b t) q h w -> b q t h w' of all L + 1 predictions; the first L are the aux_outputs."""
-        logits = [z.unflatten(0, (b, t)) for z in logits]
-        masks = [z.unflatten(0, (b, t)).transpose(1, 2) for z in masks]
-        return {"pred_logits": logits[-1], "pred_masks": masks[-1],
-                "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(logits[:-1], masks[:-1])]}
+        return layer_predictions([z.unflatten(0, (b, t)) for z in logits],
+                                 [z.unflatten(0, (b, t)).transpose(1, 2) for z in masks])
+
+    @staticmethod
+    def _train_bctq(z, b, t):
+        return z.unflatten(0, (b, t)).permute(0, 3, 1, 2)                                        # ((b t),Q,C) -> (b,C,t,Q)
 
     def _train_clips(self, N):
         """(b, t) of the (b t) frames of a training batch (…decoder.py:327-329)."""
@@ -403,8 +437,7 @@ class MultiScaleMaskedTransformerDecoder(_MaskedDecoderBase):
         if self.training:
             x, mask_features = self._train_inputs(x, mask_features)
             _, _, logits, masks = self._train_layers(x, mask_features)
-            return {"pred_logits": logits[-1], "pred_masks": masks[-1],
-                    "aux_outputs": [{"pred_logits": a, "pred_masks": m} for a, m in zip(logits[:-1], masks[:-1])]}
+            return layer_predictions(logits, masks)
         x, mask_features = self._f32_inputs(x, mask_features)
         output = self._run_layers(x, mask_features)
         _, logits, masks = self._final_heads(output, mask_features, True)
@@ -470,10 +503,10 @@ class VideoMultiScaleMaskedTransformerDecoder_dvisPlus(_MaskedDecoderBase):
         b, t = self._train_clips(x[0].shape[0])
         output, dec, logits, masks = self._train_layers(x, mask_features)
         out = self._train_video_outputs(b, t, logits, masks)
-        to_bctq = lambda z: z.unflatten(0, (b, t)).permute(0, 3, 1, 2)                           # ((b t),Q,C) -> (b,C,t,Q)
-        reid_b = to_bctq(self._train_mlp(self.reid_embed, dec))
-        out.update(pred_embds=torch.cat([to_bctq(dec), reid_b], dim=1),
-                   pred_embds_without_norm=torch.cat([to_bctq(output.transpose(0, 1)), reid_b], dim=1),
+        reid = self.reid_embed
+        reid_b = self._train_bctq(reid.train_forward(dec) if isinstance(reid, MLP) else reid(dec), b, t)   # (nn.Identity: no head)
+        out.update(pred_embds=torch.cat([self._train_bctq(dec, b, t), reid_b], dim=1),
+                   pred_embds_without_norm=torch.cat([self._train_bctq(output.transpose(0, 1), b, t), reid_b], dim=1),
                    pred_reid_embed=reid_b, mask_features=mask_features)
         return out
 
@@ -504,8 +537,7 @@ class VideoMultiScaleMaskedTransformerDecoder_dvis(_MaskedDecoderBase):
             b, t = self._train_clips(x[0].shape[0])
             output, dec, logits, masks = self._train_layers(x, mask_features)
             out = self._train_video_outputs(b, t, logits, masks)
-            to_bctq = lambda z: z.unflatten(0, (b, t)).permute(0, 3, 1, 2)                       # ((b t),Q,C) -> (b,C,t,Q)
-            out.update(pred_embds=to_bctq(dec), pred_embds_without_norm=to_bctq(output.transpose(0, 1)),
+            out.update(pred_embds=self._train_bctq(dec, b, t), pred_embds_without_norm=self._train_bctq(output.transpose(0, 1), b, t),
                        mask_features=mask_features)
             return out
         x, mask_features = self._f32_inputs(x, mask_features)
