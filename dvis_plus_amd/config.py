@@ -88,6 +88,10 @@ def get_default_cfg():
             },
             "TRACKER": {"DECODER_LAYERS": 6, "NOISE_MODE": "none", "NOISE_RATIO": 0.5},
             "REFINER": {"DECODER_LAYERS": 6},
+            # dvis_Plus/config.py:65-74 (CTMinVIS)
+            "CL_PLUGIN": {"CL_PLUGIN_NAME": "CTCLPlugin", "REID_WEIGHT": 2.0, "AUX_REID_WEIGHT": 3.0, "NUM_NEGATIVES": 99,
+                          "FUSION_LOSS": False, "BIO_CL": False, "ONE_DIRECTION": True, "MOMENTUM_EMBED": True,
+                          "NOISE_EMBED": False},
         },
         "INPUT": {"SAMPLING_FRAME_NUM": 1},
     })

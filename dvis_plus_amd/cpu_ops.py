@@ -284,3 +284,43 @@ def point_loss_sums(src, tgt, coords):
     s = x.sigmoid()
     bce = F.softplus(x) - x * t
     return torch.stack((bce.sum(-1), (s * t).sum(-1), s.sum(-1) + t.sum(-1)), dim=-1)
+
+
+# --- contrastive item losses (csrc/contrastive_items.hip) as batched torch ops ---------------------------------------------------
+def contrastive_items(src, anchor, pos_ptr, pos_idx, neg_ptr, neg_idx):
+    """functions.contrastive_items as torch ops on src's device and in its dtype (differentiable through torch autograd): src
+    (R, C); item i has the anchor row anchor[i], the positive rows pos_idx[pos_ptr[i]:pos_ptr[i + 1]] and the negative rows
+    neg_idx[neg_ptr[i]:neg_ptr[i + 1]] (int64 CPU tensors, checked by the caller) -> (reid (n), aux (n)):
+    reid = softplus(LSE_j(n_j . a) + LSE_k(-p_k . a)), the separable form of the logsumexp over all (n_j - p_k) . a and one 0 (an
+    empty side: 0); aux = (sum_k (cos(p_k, a) - 1)^2 + sum_j cos(n_j, a)^2) / (P + N) with F.normalize's cosine."""
+    dev, n = src.device, anchor.numel()
+    if n == 0:
+        return src.new_zeros(0), src.new_zeros(0)
+    a = src[anchor.to(dev)]                                                                     # (n, C)
+    ua = F.normalize(a, dim=-1)
+    aux_sum, count = src.new_zeros(n), (pos_ptr[-1:] * 0).expand(n).clone()
+    lses = []
+    for ptr, idx, sign, label in ((neg_ptr, neg_idx, 1.0, 0.0), (pos_ptr, pos_idx, -1.0, 1.0)):
+        cnt = ptr[1:] - ptr[:-1]
+        count = count + cnt
+        m = int(cnt.max())
+        if m == 0:
+            lses.append(src.new_zeros(n))
+            continue
+        item = torch.repeat_interleave(torch.arange(n), cnt)
+        col = (torch.arange(idx.numel()) - ptr[:-1][item]).to(dev)
+        item = item.to(dev)
+        x = src[idx.to(dev)]                                                                    # (slots of this side, C)
+        dot = (x * a[item]).sum(-1)
+        cos = (F.normalize(x, dim=-1) * ua[item]).sum(-1)
+        aux_sum = aux_sum.index_add(0, item, (cos - label).square())
+        # rows of an item without slots on this side are padded with zeros, not -inf: their LSE is masked out below and its
+        # gradient must not be NaN
+        pad = torch.where((cnt > 0).to(dev)[:, None], src.new_full((n, m), float("-inf")), src.new_zeros(n, m))
+        pad = pad.index_put((item, col), sign * dot)
+        lses.append(torch.logsumexp(pad, dim=1))
+    both = ((pos_ptr[1:] > pos_ptr[:-1]) & (neg_ptr[1:] > neg_ptr[:-1])).to(dev)
+    z = lses[0] + lses[1]
+    reid = torch.where(both, torch.logaddexp(z, torch.zeros_like(z)), torch.zeros_like(z))
+    aux = aux_sum / count.clamp(min=1).to(device=dev, dtype=src.dtype)
+    return reid, aux

@@ -15,6 +15,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import functions as Fn
+from .d2 import configurable
+from .registry import Registry
 from .matcher import HungarianMatcher, VideoHungarianMatcher, VideoHungarianMatcher_Consistent
 
 
@@ -254,9 +256,192 @@ def refiner_contrastive_loss(pred_embds, match, labels, memory):
     return {"loss_reid": torch.cat(reid).mean(), "loss_aux_reid": torch.cat(aux).mean()}
 
 
+class CTCLPlugin(nn.Module):
+    """CTVIS's contrastive plugin on the segmenter's "pred_reid_embed" (dvis_Plus/ctvis.py:604-799 with its train memory :451-601
+    and loss_reid :817-861): constructor arguments, ``from_config`` keys and ``weight_dict`` are the reference's.
+
+    The reference keeps a memory bank of tensor slices per video and runs ~15 tiny ops per item; here ``train_loss`` does the
+    bank's bookkeeping on indices and hands ALL items of the batch to ``Fn.contrastive_items`` in one call.  Per video and instance:
+      * frame f, instance valid: its negatives of f = ``num_negatives`` rows sampled from ``range(num_negatives + 1)`` minus its
+        matched query, sorted (the population is NOT range(Q): restated as written; num_negatives + 1 > Q raises); absent: all Q
+        rows of f;
+      * an item per frame f >= 1 where the instance is valid: anchor = its matched row of f, negatives = those of frame f - 1;
+        positive = if the instance is valid somewhere before f: the similarity-guided embedding at f - 1 when ``momentum_embed`` and
+        the coin ``np.random.rand() > 0.5`` say so, else its last valid row before f; if it is valid nowhere before f: its first valid
+        row after f — but only when f differs from the NUMBER OF ABSENT frames after f (ctvis.py:518-519 compares these two;
+        restated as written), else the item has no positive and is skipped.
+    Similarity-guided embedding (:487-513): sg_1 = e_1, sg_k = (1 - beta_k) sg_(k-1) + beta_k e_k over the valid frames, beta_k =
+    max(0, mean_(m < k) cos(e_m, e_k)), carried over absent frames; computed in torch for all instances at once (clamp(min=0): the
+    value and gradient of the reference's python max except at exactly 0, without its host sync) and appended to the rows the
+    kernel reads, so autograd carries the kernel's gradient back to "pred_reid_embed" through both.
+    Every random draw goes through ``_draw`` in the reference's order.  Host syncs: the matcher's, and one copy of the ids."""
+
+    @configurable
+    def __init__(self, *, weight_dict, num_negatives, sampling_frame_num, bio_cl, momentum_embed, noise_embed):
+        super().__init__()
+        if noise_embed:
+            raise NotImplementedError("CTCLPlugin: MODEL.CL_PLUGIN.NOISE_EMBED is not built (no config of the reference sets it)")
+        self.weight_dict = weight_dict
+        self.num_negatives = num_negatives
+        self.sampling_frame_num = sampling_frame_num
+        self.bio_cl = bio_cl
+        self.momentum_embed = momentum_embed
+        self.noise_embed = noise_embed
+        self.last_items = None            # tests: the item table of the last train_loss call
+
+    @classmethod
+    def from_config(cls, cfg):
+        cl = cfg.MODEL.CL_PLUGIN
+        return {"weight_dict": {"loss_reid": cl.REID_WEIGHT, "loss_aux_reid": cl.AUX_REID_WEIGHT},
+                "num_negatives": cl.NUM_NEGATIVES, "sampling_frame_num": cfg.INPUT.SAMPLING_FRAME_NUM, "bio_cl": cl.BIO_CL,
+                "momentum_embed": cl.MOMENTUM_EMBED, "noise_embed": cl.NOISE_EMBED}
+
+    def _draw(self, kind, *args):
+        """Every random draw of the plugin: override to replay recorded draws.
+        "negatives", population (ascending list), k -> random.sample(population, k), one per valid (video, frame, instance);
+        "momentum" -> np.random.rand(), one per item that has a valid frame before it, when momentum_embed is set."""
+        if kind == "negatives":
+            return random.sample(args[0], args[1])
+        if kind == "momentum":
+            import numpy as np
+            return float(np.random.rand())
+        raise ValueError(kind)
+
+    def match_frames(self, det_outputs, gt_instances, matcher):
+        """One matcher call per frame index over the b videos (entries i::T), in that order."""
+        T = self.sampling_frame_num
+        tensors = {k: v for k, v in det_outputs.items() if k not in ("aux_outputs", "interm_outputs") and torch.is_tensor(v)}
+        return [matcher({k: v[i::T] for k, v in tensors.items()}, gt_instances[i::T]) for i in range(T)]
+
+    def build_items(self, indices_list, valid, Q):
+        """The memory bank as index bookkeeping.  indices_list[f][v] = the matcher's (query rows, target rows) of video v in frame
+        f; valid[v] = (G_v, T) nested lists of bools -> (items, sg_rows): items = dicts with "video", "frame", "instance", "anchor"
+        (row of the (b T Q) rows), "pos" (row, or the (slot, frame) of a similarity-guided embedding when "pos_sg"), "neg" (rows);
+        sg_rows[slot] = (the T matched rows of the instance behind that slot, 0 where absent; its T valid flags)."""
+        T, K = self.sampling_frame_num, self.num_negatives
+        items, sg_slots, sg_rows = [], {}, []
+        for v, val in enumerate(valid):
+            G = len(val)
+            query = []                                   # [f][g]: the query matched to instance g in frame f
+            for f in range(T):
+                src, tgt = (t.tolist() for t in indices_list[f][v])
+                by_target = dict(zip(tgt, src))
+                query.append([by_target.get(g) for g in range(G)])
+                if any(val[g][f] and query[f][g] is None for g in range(G)):
+                    raise ValueError(f"CTCLPlugin: the matcher left a valid instance of video {v}, frame {f} without a query")
+            row = lambda f, q: (v * T + f) * Q + q
+            negatives = [[None] * G for _ in range(T)]
+            for f in range(T):
+                for g in range(G):
+                    if val[g][f]:
+                        if K + 1 > Q:
+                            raise ValueError(f"CTCLPlugin: NUM_NEGATIVES + 1 = {K + 1} exceeds the {Q} queries (the reference samples "
+                                             "its negatives from range(NUM_NEGATIVES + 1))")
+                        population = [q for q in range(K + 1) if q != query[f][g]]
+                        negatives[f][g] = [row(f, q) for q in sorted(self._draw("negatives", population, K))]
+                    else:
+                        negatives[f][g] = [row(f, q) for q in range(Q)]
+            for f in range(1, T):
+                for g in range(G):
+                    if not val[g][f]:
+                        continue
+                    before = [m for m in range(f) if val[g][m]]
+                    pos, pos_sg = None, False
+                    if before:
+                        if self.momentum_embed and self._draw("momentum") > 0.5:
+                            if (v, g) not in sg_slots:
+                                sg_slots[v, g] = len(sg_rows)
+                                sg_rows.append(([row(m, query[m][g]) if val[g][m] else 0 for m in range(T)], val[g]))
+                            pos, pos_sg = (sg_slots[v, g], f - 1), True
+                        else:
+                            pos = row(before[-1], query[before[-1]][g])
+                    elif f != sum(1 for m in range(f + 1, T) if not val[g][m]):       # ctvis.py:518-519, as written
+                        after = [m for m in range(f + 1, T) if val[g][m]]
+                        if after:
+                            pos = row(after[0], query[after[0]][g])
+                    if pos is None:
+                        continue
+                    items.append({"video": v, "frame": f, "instance": g, "anchor": row(f, query[f][g]), "pos": pos,
+                                  "pos_sg": pos_sg, "neg": negatives[f - 1][g]})
+        return items, sg_rows
+
+    def similarity_guided(self, reid, rows, valid):
+        """reid (b T Q, C); rows (I, T) int64 the instances' matched rows (any row where absent), valid (I, T) bool (both on
+        reid's device) -> (I, T, C): the similarity-guided embedding after each frame (zeros before the first valid frame)."""
+        I, T = rows.shape
+        e = reid[rows]                                                                           # (I, T, C)
+        u = F.normalize(e, dim=-1)
+        cos = u @ u.transpose(1, 2)                                                              # [i, m, k]
+        pair = (valid[:, :, None] & valid[:, None, :]).to(e.dtype) * torch.triu(torch.ones(T, T, dtype=e.dtype, device=e.device), 1)
+        before = (valid.to(torch.int64).cumsum(1) - valid.to(torch.int64))                      # valid frames before k
+        beta = ((cos * pair).sum(1) / before.clamp(min=1).to(e.dtype)).clamp(min=0)
+        beta = torch.where(valid, torch.where(before == 0, torch.ones_like(beta), beta), torch.zeros_like(beta))
+        sg, out = torch.zeros_like(e[:, 0]), []
+        for k in range(T):
+            b = beta[:, k, None]
+            sg = (1 - b) * sg + b * e[:, k]
+            out.append(sg)
+        return torch.stack(out, dim=1)
+
+    def get_reid_loss(self, reid, indices_list, gt_instances):
+        """reid ((b T), Q, C), the per-frame matches and the (b T) per-frame targets -> {"loss_reid", "loss_aux_reid"} unweighted."""
+        T = self.sampling_frame_num
+        BT, Q, C = reid.shape
+        b = BT // T
+        dev = reid.device
+        zero = lambda: {"loss_reid": reid.sum() * 0, "loss_aux_reid": reid.sum() * 0}
+        G = [int(gt_instances[v * T]["ids"].shape[0]) for v in range(b)]
+        if sum(G) == 0:
+            self.last_items = []
+            return zero()
+        ids = torch.cat([gt_instances[v * T + f]["ids"].reshape(-1) for v in range(b) for f in range(T)]).tolist()      # the one copy
+        valid, off = [], 0
+        for v in range(b):
+            frames = [ids[off + f * G[v]:off + (f + 1) * G[v]] for f in range(T)]
+            off += T * G[v]
+            valid.append([[frames[f][g] != -1 for f in range(T)] for g in range(G[v])])
+        items, sg_rows = self.build_items(indices_list, valid, Q)
+        self.last_items = items
+        if not items:
+            return zero()
+        src = reid.reshape(BT * Q, C)
+        if src.dtype != torch.float32 and src.is_cuda:
+            src = src.float()
+        if sg_rows:
+            sg = self.similarity_guided(src, torch.tensor([r for r, _ in sg_rows], device=dev),
+                                        torch.tensor([v for _, v in sg_rows], device=dev))
+            src = torch.cat([src, sg.reshape(-1, C)], dim=0)
+        n = len(items)
+        pos = [BT * Q + it["pos"][0] * T + it["pos"][1] if it["pos_sg"] else it["pos"] for it in items]
+        neg_ptr = [0]
+        for it in items:
+            neg_ptr.append(neg_ptr[-1] + len(it["neg"]))
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32)
+        reid_i, aux_i = Fn.contrastive_items(src.contiguous(), i32([it["anchor"] for it in items]), torch.arange(n + 1, dtype=torch.int32),
+                                             i32(pos), i32(neg_ptr), i32([r for it in items for r in it["neg"]]))
+        return {"loss_reid": reid_i.sum() / n, "loss_aux_reid": aux_i.sum() / n}
+
+    def train_loss(self, det_outputs, gt_instances, matcher):
+        """det_outputs: "pred_logits" ((b T), Q, K + 1), "pred_masks" ((b T), Q, h, w), "pred_reid_embed" ((b T), Q, C);
+        gt_instances: the (b T) per-frame targets ("labels", "ids" (G), "masks" (G, h, w)); matcher: the image matcher.
+        -> the two weighted losses."""
+        indices_list = self.match_frames(det_outputs, gt_instances, matcher)
+        losses = self.get_reid_loss(det_outputs["pred_reid_embed"], indices_list, gt_instances)
+        return {k: v * self.weight_dict[k] for k, v in losses.items() if k in self.weight_dict}
+
+
+CL_PLUGIN_REGISTRY = Registry("CL_PLUGIN")
+CL_PLUGIN_REGISTRY.register(CTCLPlugin)
+
+
+def build_cl_plugin(cfg):
+    """ctvis.py:447-449."""
+    return CL_PLUGIN_REGISTRY.get(cfg.MODEL.CL_PLUGIN.CL_PLUGIN_NAME)(cfg)
+
+
 def build_criterion(cfg, meta_arch=None):
     """The criterion the reference's ``from_config`` of `meta_arch` builds (MODEL.META_ARCHITECTURE when None): "MinVIS"
-    (dvis_Plus/meta_architecture.py:105-138), "DVIS_Plus_online" (:516-571), "DVIS_Plus_offline" (:1175-1243), "MaskFormer"
+    (dvis_Plus/meta_architecture.py:105-138) and "CTMinVIS" (the same), "DVIS_Plus_online" (:516-571), "DVIS_Plus_offline" (:1175-1243), "MaskFormer"
     (mask2former/maskformer_model.py:100-162) — matcher class, weights, weight_dict with its deep-supervision copies, losses."""
     meta_arch = cfg.MODEL.META_ARCHITECTURE if meta_arch is None else meta_arch
     if not isinstance(meta_arch, str):
@@ -264,7 +449,7 @@ def build_criterion(cfg, meta_arch=None):
     mf = cfg.MODEL.MASK_FORMER
     weights = {"cost_class": mf.CLASS_WEIGHT, "cost_mask": mf.MASK_WEIGHT, "cost_dice": mf.DICE_WEIGHT}
     num_points, use_cl = mf.TRAIN_NUM_POINTS, False
-    if meta_arch == "MinVIS":
+    if meta_arch in ("MinVIS", "CTMinVIS"):              # ctvis.py:105-155 builds MinVIS's criterion
         matcher = VideoHungarianMatcher(num_points=num_points, **weights)
     elif meta_arch == "DVIS_Plus_online":
         matcher = VideoHungarianMatcher_Consistent(num_points=num_points, frames=cfg.INPUT.SAMPLING_FRAME_NUM, **weights)

@@ -3280,3 +3280,185 @@ def point_mask_losses(src, tgt, coords, num_masks, deterministic=None):
         raise RuntimeError(f"point_mask_losses: {src.shape[0]} rows (at most 65535 per call)")
     t, u8 = _target_maps(tgt.detach(), dev)
     return PointMaskLossFunction.apply(x.contiguous(), t, u8, _coords_f32(coords.detach(), dev), num_masks, deterministic)
+
+
+# --- contrastive item losses of CTVIS's CTCLPlugin (csrc/contrastive_items.hip) ---------------------------------------------------
+# Item i = anchor row anchor[i] of src (R, C), positive rows pos_idx[pos_ptr[i]:pos_ptr[i + 1]], negative rows
+# neg_idx[neg_ptr[i]:neg_ptr[i + 1]] (integer tensors; they originate on the host and are best handed over as CPU tensors: they
+# are checked there, and GPU ones are copied back first).  Dispatch by device: a GPU tensor runs the kernels or the call raises, a
+# CPU tensor takes cpu_ops.contrastive_items.  DVIS_CONTRASTIVE_ITEMS=0 selects the torch formulation on the GPU as well (timing
+# tool and the tests' comparison).
+def contrastive_items_transpose(anchor, pos_ptr, pos_idx, neg_ptr, neg_idx, R):
+    """The backward's transposed incidence lists, built on the host from CPU index tensors (pure: no GPU, no library).
+    -> (row_ptr (R + 1), occ_slot, occ_item, arow_ptr (R + 1), arow_item) int32: row r occurs as a positive / negative at
+    occ_slot[row_ptr[r]:row_ptr[r + 1]] (global slot numbers: item i's slots start at pos_ptr[i] + neg_ptr[i], positives first) of the
+    items occ_item[...], in (item, slot) order, and anchors the items arow_item[arow_ptr[r]:arow_ptr[r + 1]], ascending."""
+    i64 = lambda t: torch.as_tensor(t).to(device="cpu", dtype=torch.int64)
+    anchor, pos_ptr, pos_idx, neg_ptr, neg_idx = (i64(t) for t in (anchor, pos_ptr, pos_idx, neg_ptr, neg_idx))
+    n = anchor.numel()
+    items = torch.arange(n)
+    P, N = pos_ptr[1:] - pos_ptr[:-1], neg_ptr[1:] - neg_ptr[:-1]
+    base = pos_ptr[:-1] + neg_ptr[:-1]
+    item_p, item_n = torch.repeat_interleave(items, P), torch.repeat_interleave(items, N)
+    slot_p = base[item_p] + torch.arange(pos_idx.numel()) - pos_ptr[:-1][item_p]
+    slot_n = base[item_n] + P[item_n] + torch.arange(neg_idx.numel()) - neg_ptr[:-1][item_n]
+    rows, slots, item = torch.cat((pos_idx, neg_idx)), torch.cat((slot_p, slot_n)), torch.cat((item_p, item_n))
+    S = max(int(slots.numel()), 1)
+    order = torch.argsort(rows * S + slots)               # global slot numbers ascend with (item, slot)
+    ptr = lambda r: torch.cat((torch.zeros(1, dtype=torch.int64), torch.bincount(r, minlength=R).cumsum(0)))
+    a_order = torch.argsort(anchor, stable=True)
+    i32 = lambda t: t.to(torch.int32)
+    return i32(ptr(rows)), i32(slots[order]), i32(item[order]), i32(ptr(anchor)), i32(a_order)
+
+
+class _ContrastiveItemLists:
+    """The checked index lists of one call: host copies, the device copy (one upload), and on demand the transposed lists."""
+
+    def __init__(self, op, R, anchor, pos_ptr, pos_idx, neg_ptr, neg_idx):
+        lists = []
+        for name, t in (("anchor", anchor), ("pos_ptr", pos_ptr), ("pos_idx", pos_idx), ("neg_ptr", neg_ptr), ("neg_idx", neg_idx)):
+            t = torch.as_tensor(t)
+            if t.dim() != 1 or t.dtype not in (torch.int32, torch.int64):
+                raise RuntimeError(f"{op}: {name} must be a 1-d int32 / int64 tensor (got {tuple(t.shape)}, {t.dtype})")
+            lists.append(t.detach().to(device="cpu", dtype=torch.int64))
+        anchor, pos_ptr, pos_idx, neg_ptr, neg_idx = lists
+        n = anchor.numel()
+        for name, ptr, idx in (("pos", pos_ptr, pos_idx), ("neg", neg_ptr, neg_idx)):
+            if ptr.numel() != n + 1 or int(ptr[0]) != 0 or int(ptr[-1]) != idx.numel() or bool((ptr[1:] < ptr[:-1]).any()):
+                raise RuntimeError(f"{op}: {name}_ptr must have n + 1 = {n + 1} non-decreasing entries from 0 to len({name}_idx) = "
+                                   f"{idx.numel()}")
+        for name, idx in (("anchor", anchor), ("pos_idx", pos_idx), ("neg_idx", neg_idx)):
+            if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= R):
+                raise RuntimeError(f"{op}: {name} holds a row index outside [0, {R})")
+        self.R, self.n, self.S, self.host = R, n, pos_idx.numel() + neg_idx.numel(), lists
+        if self.S >= 2 ** 31 or R >= 2 ** 31:
+            raise RuntimeError(f"{op}: {self.S} slots / {R} rows (fewer than 2^31 each)")
+        self.dev = self.dev_t = None
+
+    @staticmethod
+    def _upload(parts, device):
+        # every part starts on a 4-int boundary of ONE int32 buffer: one host-to-device copy
+        sizes = [(p.numel() + 3) // 4 * 4 for p in parts]
+        buf = torch.zeros(max(sum(sizes), 4), dtype=torch.int32)
+        views, off = [], 0
+        for p, s in zip(parts, sizes):
+            buf[off:off + p.numel()] = p
+            views.append((off, p.numel()))
+            off += s
+        buf = buf.to(device)
+        return [buf[o:o + k] for o, k in views]
+
+    def device(self, device):
+        if self.dev is None:
+            self.dev = self._upload(self.host, device)
+        return self.dev
+
+    def transposed(self, device):
+        if self.dev_t is None:
+            self.dev_t = self._upload(contrastive_items_transpose(*self.host, self.R), device)
+        return self.dev_t
+
+
+def _contrastive_items_iptr(view):
+    """Device pointer of a slice of the uploaded index buffer (an EMPTY list still gets its place in the buffer, not null)."""
+    return ctypes.c_void_p(view.untyped_storage().data_ptr() + 4 * view.storage_offset())
+
+
+def _contrastive_items_src_check(op, src):
+    if not (src.dim() == 2 and src.dtype == torch.float32 and src.is_contiguous() and src.shape[1] % 4 == 0 and src.shape[0] >= 1):
+        raise RuntimeError(f"{op}: src must be a contiguous float32 (R, C) tensor with R >= 1 and C % 4 == 0 (got "
+                           f"{tuple(src.shape)}, {src.dtype}, contiguous {src.is_contiguous()})")
+
+
+def _contrastive_items_on_kernel(src):
+    return src.is_cuda and os.environ.get("DVIS_CONTRASTIVE_ITEMS", "1") != "0"
+
+
+def _contrastive_items_kernel(src, lists):
+    """-> (reid (n), aux (n), saved = (dots (S), norms (S), stats (n, 3)))."""
+    dev, n, S = src.device, lists.n, lists.S
+    f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    reid, aux, dots, norms, stats = f(n), f(n), f(max(S, 1)), f(max(S, 1)), f(max(n, 1), 3)
+    if n == 0:
+        return reid, aux, (dots, norms, stats)
+    d = lists.device(dev)
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_contrastive_items(
+            native.dev_ptr(src, "src"), src.shape[0], src.shape[1], *(_contrastive_items_iptr(t) for t in d), n, S,
+            native.dev_ptr(reid, "reid"), native.dev_ptr(aux, "aux"), native.dev_ptr(dots, "dots"), native.dev_ptr(norms, "norms"),
+            native.dev_ptr(stats, "stats"), native.stream_ptr(dev))
+    native.check(rc, "dvis_contrastive_items")
+    return reid, aux, (dots, norms, stats)
+
+
+def _contrastive_items_backward_kernel(src, lists, saved, grad_reid, grad_aux):
+    dev, n, S = src.device, lists.n, lists.S
+    R, C = src.shape
+    if n == 0:
+        return torch.zeros_like(src)
+    dots, norms, stats = saved
+    g = [t.detach().to(device=dev, dtype=torch.float32).expand(n).contiguous() for t in (grad_reid, grad_aux)]
+    if not (dots.is_cuda and dots.numel() >= S and norms.numel() >= S and stats.numel() >= 3 * n):
+        raise RuntimeError("contrastive_items_backward: `saved` is not what contrastive_items(..., return_saved=True) returned for these lists")
+    lib = native.lib()
+    grad_src = torch.empty_like(src)
+    ws = torch.empty((max(lib.dvis_contrastive_items_backward_ws_bytes(n, S, C), 16) // 4,), dtype=torch.float32, device=dev)
+    d, t = lists.device(dev), lists.transposed(dev)
+    with torch.cuda.device(dev):
+        rc = lib.dvis_contrastive_items_backward(
+            native.dev_ptr(src, "src"), R, C, *(_contrastive_items_iptr(t) for t in d), n, S,
+            *(_contrastive_items_iptr(x) for x in t), native.dev_ptr(dots, "dots"),
+            native.dev_ptr(norms, "norms"), native.dev_ptr(stats, "stats"), native.dev_ptr(g[0], "grad_reid"),
+            native.dev_ptr(g[1], "grad_aux"), native.dev_ptr(grad_src, "grad_src"), native.dev_ptr(ws, "workspace"),
+            native.stream_ptr(dev))
+    native.check(rc, "dvis_contrastive_items_backward")
+    return grad_src
+
+
+def contrastive_items_backward(src, anchor, pos_ptr, pos_idx, neg_ptr, neg_idx, saved, grad_reid, grad_aux):
+    """Backward of ``contrastive_items`` on the kernels: saved = the forward's (dots, norms, stats), grad_reid / grad_aux (n) ->
+    grad_src (R, C).  Exact fp32 without atomics, the same bits on every call; rows that no item references get exactly 0."""
+    _contrastive_items_src_check("contrastive_items_backward", src)
+    if not src.is_cuda:
+        raise RuntimeError("contrastive_items_backward: the explicit backward runs the kernels: src must be a GPU tensor")
+    lists = _ContrastiveItemLists("contrastive_items_backward", src.shape[0], anchor, pos_ptr, pos_idx, neg_ptr, neg_idx)
+    return _contrastive_items_backward_kernel(src.detach(), lists, saved, grad_reid, grad_aux)
+
+
+class ContrastiveItemsFunction(Function):
+    """``contrastive_items`` under autograd: the forward kernel saves one dot and one norm per slot and three floats per item (never
+    a gather of rows); the transposed lists are built on the host while the forward runs."""
+
+    @staticmethod
+    def forward(ctx, src, lists):
+        reid, aux, saved = _contrastive_items_kernel(src, lists)
+        if lists.n:
+            lists.transposed(src.device)
+        ctx.save_for_backward(src, *saved)
+        ctx.lists = lists
+        return reid, aux
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_reid, grad_aux):
+        src, *saved = ctx.saved_tensors
+        return _contrastive_items_backward_kernel(src, ctx.lists, saved, grad_reid, grad_aux), None
+
+
+def contrastive_items(src, anchor, pos_ptr, pos_idx, neg_ptr, neg_idx, return_saved=False):
+    """Per-item contrastive losses (ctvis.py's loss_reid before the division by the item count): src (R, C) fp32 ->
+    reid (n) = logsumexp over all (negative - positive) . anchor pairs and one 0, aux (n) = mean squared difference between
+    F.normalize's cosine and the label (1 positive, 0 negative).  One kernel launch for all items; with grad enabled and a src that
+    requires grad the call goes through ContrastiveItemsFunction.  n = 0: two empty vectors, nothing is launched.
+    return_saved: also the kernels' saved tensors, for ``contrastive_items_backward`` (GPU, no autograd)."""
+    if src.dim() == 2 and src.is_floating_point() and src.shape[0] >= 1 and not _contrastive_items_on_kernel(src) and not return_saved:
+        lists = _ContrastiveItemLists("contrastive_items", src.shape[0], anchor, pos_ptr, pos_idx, neg_ptr, neg_idx)
+        return cpu_ops.contrastive_items(src, *lists.host)
+    _contrastive_items_src_check("contrastive_items", src)
+    if not src.is_cuda:
+        raise RuntimeError("contrastive_items: return_saved needs the kernels: src must be a GPU tensor")
+    lists = _ContrastiveItemLists("contrastive_items", src.shape[0], anchor, pos_ptr, pos_idx, neg_ptr, neg_idx)
+    if torch.is_grad_enabled() and src.requires_grad and not return_saved:
+        return ContrastiveItemsFunction.apply(src, lists)
+    reid, aux, saved = _contrastive_items_kernel(src.detach(), lists)
+    return (reid, aux, saved) if return_saved else (reid, aux)

@@ -424,7 +424,17 @@ class MinVIS(_VideoBase):
         targets = self.prepare_targets(batched_inputs, images)
         outputs, targets = self.frame_decoder_loss_reshape(outputs, targets)
         losses = self.criterion(outputs, targets)
-        return self._weighted(losses)
+        losses = self._weighted(losses)
+        losses.update(self._plugin_losses(outputs, targets))
+        return losses
+
+    def _plugin_losses(self, outputs, targets):
+        """Weighted losses a subclass adds behind the set losses (CTMinVIS's contrastive plugin); none here."""
+        return {}
+
+    def _alignment_embeds(self, pred, dec):
+        """The per-frame embeddings (T, Q, C) the evaluation's alignment chain runs on: the decoder embeddings."""
+        return dec
 
     def _train_backbone(self, images):
         """The backbone's training forward.  A backbone whose frozen part runs on the split-f16 inference kernels under
@@ -482,7 +492,8 @@ class MinVIS(_VideoBase):
         # ---- alignment chain: frame 0 keeps its order, frame t is matched to the ALIGNED frame t-1
         idx = torch.arange(Q, device=dec.device).unsqueeze(0).repeat(T, 1)
         if T > 1:
-            nrm = dec / dec.norm(dim=-1, keepdim=True)
+            align = self._alignment_embeds(pred, dec)
+            nrm = align / align.norm(dim=-1, keepdim=True)
             cost = 1 - torch.bmm(nrm[1:], nrm[:-1].transpose(1, 2))                    # (T-1, Q, Q): cur x previous
             idx[1:] = torch.from_numpy(match_chain(cost)).to(dec.device)
         ar = torch.arange(T, device=dec.device)[:, None]
@@ -496,6 +507,54 @@ class MinVIS(_VideoBase):
         out = {"image_size": tuple(out_hw), "pred_scores": scores.tolist(), "pred_labels": labels.tolist(),
                "pred_masks": [m for m in masks], "pred_ids": slot.tolist(), "aligned_indices": idx}
         return PP.to_reference_format(out) if self.reference_outputs else out
+
+
+@META_ARCH_REGISTRY.register()
+class CTMinVIS(MinVIS):
+    """CTVIS's segmenter stage (dvis_Plus/ctvis.py:30-442), what every CTVIS_*.yaml trains and the DVIS++ checkpoints start from:
+    MinVIS plus the contrastive plugin ``CTCLPlugin`` on the `_dvisPlus` decoder's "pred_reid_embed" in training (``image_matcher``
+    assigns queries frame by frame for it), and the alignment chain run on the reid embeddings at test time (:293-340).  Only the
+    VIS inference path, as in the reference."""
+
+    @configurable
+    def __init__(self, *, image_matcher=None, cl_plugin=None, **kwargs):
+        super().__init__(**kwargs)
+        self.image_matcher, self.cl_plugin = image_matcher, cl_plugin
+
+    @classmethod
+    def from_config(cls, cfg):
+        """ctvis.py:105-175."""
+        ret = super().from_config(cfg)
+        ret.update(image_matcher=None, cl_plugin=None)
+        mf = cfg.MODEL.MASK_FORMER
+        if "CLASS_WEIGHT" in mf:
+            from .criterion import build_cl_plugin
+            from .matcher import HungarianMatcher
+            ret["image_matcher"] = HungarianMatcher(cost_class=mf.CLASS_WEIGHT, cost_mask=mf.MASK_WEIGHT, cost_dice=mf.DICE_WEIGHT,
+                                                    num_points=mf.TRAIN_NUM_POINTS)
+            ret["cl_plugin"] = build_cl_plugin(cfg)
+        return ret
+
+    @staticmethod
+    def prepare_for_cl_plugin(outputs, targets):
+        """ctvis.py:181-188 without its in-place edits: the last layer's predictions with the frame axis of masks and ids squeezed
+        and "pred_reid_embed" as 'b c t q -> (b t) q c'; no aux and no embedding entries."""
+        det = {"pred_logits": outputs["pred_logits"], "pred_masks": outputs["pred_masks"].squeeze(2),
+               "pred_reid_embed": outputs["pred_reid_embed"].permute(0, 2, 3, 1).flatten(0, 1)}
+        gt = [{"labels": t["labels"], "ids": t["ids"].squeeze(1), "masks": t["masks"].squeeze(1)} for t in targets]
+        return det, gt
+
+    def _plugin_losses(self, outputs, targets):
+        if self.cl_plugin is None or self.image_matcher is None:
+            raise RuntimeError("CTMinVIS.train() needs image_matcher and cl_plugin (from_config builds them)")
+        if "pred_reid_embed" not in outputs:
+            raise RuntimeError("CTMinVIS.train(): the decoder returns no 'pred_reid_embed' (CTVIS configs take "
+                               "VideoMultiScaleMaskedTransformerDecoder_dvisPlus)")
+        det_outputs, gt_instances = self.prepare_for_cl_plugin(outputs, targets)
+        return self.cl_plugin.train_loss(det_outputs, gt_instances, self.image_matcher)
+
+    def _alignment_embeds(self, pred, dec):
+        return pred.reid_embed(dec)
 
 
 @META_ARCH_REGISTRY.register()

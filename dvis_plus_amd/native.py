@@ -165,6 +165,11 @@ SIGNATURES = {
     "dvis_point_loss_ws_bytes": (_i64, [_i64]),
     "dvis_point_loss_fwd": (_i, [_p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "dvis_point_loss_bwd": (_i, [_p, _p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p]),
+    "dvis_contrastive_items_tile": (_i, []),
+    "dvis_contrastive_items": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p]),
+    "dvis_contrastive_items_backward_ws_bytes": (_i64, [_i, _i64, _i]),
+    "dvis_contrastive_items_backward": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                             _p, _p, _p]),
 }
 
 _lib = None

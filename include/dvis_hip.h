@@ -976,6 +976,33 @@ int dvis_point_loss_bwd(const float *src, const void *tgt, int tgt_u8, const flo
                         const float *g_dice, int R, int P, int H, int W, int Ht, int Wt, float num_masks, float *grad_src,
                         void *det_ws, void *stream);
 
+/*
+ * Contrastive item losses of CTVIS's CTCLPlugin (csrc/contrastive_items.hip; dvis_Plus/ctvis.py:753-769, 817-861).
+ * src (R, C) fp32, C % 4 == 0, 16-byte aligned.  Item i of n: anchor row anchor[i], positive rows pos_idx[pos_ptr[i] .. pos_ptr[i + 1]),
+ * negative rows neg_idx[neg_ptr[i] .. neg_ptr[i + 1]) (int32, device; ptr arrays non-decreasing from 0, indices in [0, R): the
+ * caller checks them where the lists still live on the host, the kernels clamp).  S = pos_ptr[n] + neg_ptr[n] slots in all; slot s
+ * of item i (positives first) has the global number pos_ptr[i] + neg_ptr[i] + s.
+ * dvis_contrastive_items: one launch ->  reid (n) = softplus(LSE_j(n_j . a) + LSE_k(-p_k . a)) (0 for an empty side),
+ *   aux (n) = (sum_k (cos(p_k, a) - 1)^2 + sum_j cos(n_j, a)^2) / (P_i + N_i) with F.normalize's cosine (norms clamped at 1e-12);
+ *   saved for the backward: dots (S), norms (S) per slot and stats (n, 3) = [LSE_neg, LSE_pos, |a|].  n = 0 launches nothing.
+ * dvis_contrastive_items_backward: grad_src (R, C), every row written once (rows no item references: exactly 0), of
+ *   sum_i grad_reid[i] reid[i] + grad_aux[i] aux[i].  row_ptr (R + 1) / occ_slot / occ_item: per source row its occurrences as a
+ *   positive or negative, as (global slot, item), in (item, slot) order; arow_ptr (R + 1) / arow_item: the items a row anchors,
+ *   ascending (functions.contrastive_items_transpose builds both on the host).  ws: dvis_contrastive_items_backward_ws_bytes(n,
+ *   S, C) bytes, 16-byte aligned (-1 for bad sizes).  Exact fp32, no atomics, fixed reduction order: the same bits every call.
+ * dvis_contrastive_items_tile: the slots one pass of a workgroup's per-item reductions covers.
+ */
+int dvis_contrastive_items_tile(void);
+int dvis_contrastive_items(const float *src, int64_t R, int C, const int32_t *anchor, const int32_t *pos_ptr, const int32_t *pos_idx,
+                           const int32_t *neg_ptr, const int32_t *neg_idx, int n, int64_t S, float *reid, float *aux, float *dots,
+                           float *norms, float *stats, void *stream);
+int64_t dvis_contrastive_items_backward_ws_bytes(int n, int64_t S, int C);
+int dvis_contrastive_items_backward(const float *src, int64_t R, int C, const int32_t *anchor, const int32_t *pos_ptr,
+                                    const int32_t *pos_idx, const int32_t *neg_ptr, const int32_t *neg_idx, int n, int64_t S,
+                                    const int32_t *row_ptr, const int32_t *occ_slot, const int32_t *occ_item, const int32_t *arow_ptr,
+                                    const int32_t *arow_item, const float *dots, const float *norms, const float *stats,
+                                    const float *grad_reid, const float *grad_aux, float *grad_src, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
