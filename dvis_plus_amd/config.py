@@ -69,6 +69,11 @@ def get_default_cfg():
             "BACKBONE": {"NAME": "build_resnet_backbone"},
             "VIT_ADAPTER": {"NAME": "vitl", "VIT_WEIGHT": None, "FREEZE_VIT": True, "FINETUNE": False,
                             "FINETUNE_INDEXES": [0], "WITH_CP": False},
+            # mask2former/config.py:74-90 (D2SwinTransformer, swin.py)
+            "SWIN": {"PRETRAIN_IMG_SIZE": 224, "PATCH_SIZE": 4, "EMBED_DIM": 96, "DEPTHS": [2, 2, 6, 2], "NUM_HEADS": [3, 6, 12, 24],
+                     "WINDOW_SIZE": 7, "MLP_RATIO": 4.0, "QKV_BIAS": True, "QK_SCALE": None, "DROP_RATE": 0.0, "ATTN_DROP_RATE": 0.0,
+                     "DROP_PATH_RATE": 0.3, "APE": False, "PATCH_NORM": True, "OUT_FEATURES": ["res2", "res3", "res4", "res5"],
+                     "USE_CHECKPOINT": False},
             "PIXEL_MEAN": [123.675, 116.280, 103.530],
             "PIXEL_STD": [58.395, 57.120, 57.375],
             "SEM_SEG_HEAD": {

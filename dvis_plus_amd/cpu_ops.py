@@ -324,3 +324,38 @@ def contrastive_items(src, anchor, pos_ptr, pos_idx, neg_ptr, neg_idx):
     reid = torch.where(both, torch.logaddexp(z, torch.zeros_like(z)), torch.zeros_like(z))
     aux = aux_sum / count.clamp(min=1).to(device=dev, dtype=src.dtype)
     return reid, aux
+
+
+# --- shifted-window attention of the Swin backbone (csrc/window_attention.hip) ------------------------------------------------
+def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale=None):
+    """functions.window_attention as torch ops on qkv's device and in its dtype — the contract of dvis_window_attention
+    (include/dvis_hip.h), which is what swin.py:235-295 computes around WindowAttention.forward: qkv (B, H W, 3 C) on the unpadded
+    grid, columns [3][heads][d]; the token at shifted coordinate (ys, xs) is source ((ys + shift) % Hp, (xs + shift) % Wp), a source
+    at or beyond (H, W) is a pad token with q / k / v = qkv_bias (zeros when None); per window and head softmax(scale q k^T +
+    table[relative position] - 100 [regions differ, shift > 0]) v; rows are written at un-padded sources only -> (B, H W, C)."""
+    C = qkv.shape[-1] // 3
+    d, N, dev = C // heads, ws * ws, qkv.device
+    scale = d ** -0.5 if scale is None else scale
+    nh, nw = -(-H // ws), -(-W // ws)
+    Hp, Wp = nh * ws, nw * ws
+    ys, xs = torch.arange(Hp, device=dev), torch.arange(Wp, device=dev)
+    sy, sx = (ys + shift) % Hp, (xs + shift) % Wp
+    valid = ((sy < H)[:, None] & (sx < W)[None, :]).reshape(-1)                                  # per shifted coordinate
+    src = torch.where(valid, (sy[:, None] * W + sx[None, :]).reshape(-1), torch.full((), H * W, device=dev))
+    pad = qkv.new_zeros(3 * C) if qkv_bias is None else qkv_bias.to(qkv.dtype)
+    rows = torch.cat([qkv.reshape(B, H * W, 3 * C), pad.expand(B, 1, 3 * C)], dim=1)[:, src]     # (B, Hp Wp, 3 C), shifted order
+    q, k, v = rows.view(B, nh, ws, nw, ws, 3, heads, d).permute(5, 0, 1, 3, 6, 2, 4, 7).reshape(3, B, nh * nw, heads, N, d)
+    attn = (q * scale) @ k.transpose(-2, -1)                                                      # (B, nW, heads, N, N)
+    ly, lx = torch.arange(N, device=dev) // ws, torch.arange(N, device=dev) % ws
+    index = (ly[:, None] - ly[None, :] + ws - 1) * (2 * ws - 1) + (lx[:, None] - lx[None, :] + ws - 1)
+    attn = attn + bias_table.to(qkv.dtype)[index.reshape(-1)].view(N, N, heads).permute(2, 0, 1)
+    if shift > 0:
+        r = lambda n, size: (n >= size - ws).long() + (n >= size - shift).long()
+        region = (3 * r(ys, Hp)[:, None] + r(xs, Wp)[None, :]).view(nh, ws, nw, ws).permute(0, 2, 1, 3).reshape(nh * nw, N)
+        differ = region[:, :, None] != region[:, None, :]
+        attn = attn + torch.where(differ, -100.0, 0.0).to(qkv.dtype)[None, :, None]
+    o = torch.softmax(attn, dim=-1) @ v                                                           # (B, nW, heads, N, d)
+    o = o.view(B, nh, nw, heads, ws, ws, d).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, Hp * Wp, C)
+    out = qkv.new_empty(B, H * W, C)
+    out[:, src[valid]] = o[:, valid]
+    return out

@@ -909,6 +909,55 @@ def masked_attention(q, k, v, nheads, mask=None, allowed_count=None):
     return _attention_kernel(q, k, v, nheads, mask, allowed_count)
 
 
+def window_attention_supported(ws, d):
+    """Whether csrc/window_attention.hip serves window size `ws` at head dim `d` (asked of the library itself)."""
+    return bool(native.lib().dvis_window_attention_supported(int(ws), int(d)))
+
+
+def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale=None, out=None):
+    """Swin's shifted-window attention on the block's qkv projection (swin.py:131-171, 235-295, 413-440): pad, cyclic shift, window
+    partition, per-head relative-position bias, region mask, softmax, P V, window reverse, reverse shift and crop in ONE kernel
+    (csrc/window_attention.hip; the contract is spelled out at dvis_window_attention in include/dvis_hip.h).
+    qkv (B, H W, 3 C) on the UNPADDED token grid, columns [3][heads][d]; qkv_bias (3 C) or None: what a pad token's q / k / v is (the
+    reference pads after norm1); bias_table ((2 ws - 1)^2, heads), raw; 0 <= shift < ws; scale defaults to d^-0.5.
+    -> (B, H W, C), columns [heads][d], ready for the out-projection (written into `out`, a contiguous fp32 GPU tensor of that shape,
+    when given: every row of it is written).
+    fp32 contiguous GPU tensors run the kernel; a (ws, d) it does not serve raises (DVIS_STRICT=0: cpu_ops.window_attention's torch
+    formulation on the GPU).  CPU tensors (any float dtype) take cpu_ops.window_attention.  There is no backward: an input that
+    requires grad on the GPU raises."""
+    tensors = [t for t in (qkv, qkv_bias, bias_table) if t is not None]
+    C = qkv.shape[-1] // 3
+    d = C // heads
+    if qkv.dim() != 3 or tuple(qkv.shape) != (B, H * W, 3 * heads * d) or tuple(bias_table.shape) != ((2 * ws - 1) ** 2, heads) \
+            or (qkv_bias is not None and tuple(qkv_bias.shape) != (3 * C,)) or not 0 <= shift < ws:
+        raise RuntimeError(f"window_attention: expected qkv (B, H W, 3 heads d), qkv_bias (3 C), bias_table ((2 ws - 1)^2, heads) and "
+                           f"0 <= shift < ws; got qkv {tuple(qkv.shape)}, bias_table {tuple(bias_table.shape)}, B={B} H={H} W={W} "
+                           f"heads={heads} ws={ws} shift={shift}")
+    if _on_cpu(*tensors):
+        return cpu_ops.window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("window_attention: there is no window-attention backward (csrc/window_attention.hip is inference-only); "
+                           "call it under torch.no_grad() or detach qkv, qkv_bias and bias_table")
+    for name, t in (("qkv", qkv), ("qkv_bias", qkv_bias), ("bias_table", bias_table)):
+        if t is not None and not (t.is_cuda and t.device == qkv.device and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f"window_attention: {name} must be a contiguous float32 tensor on qkv's GPU (got {t.dtype} on {t.device}, "
+                               f"contiguous {t.is_contiguous()})")
+    scale = float(d ** -0.5 if scale is None else scale)
+    if not window_attention_supported(ws, d):
+        _torch_path("window_attention", qkv, f"the kernel does not serve window size ws={ws} with head dim d={d}: d=32 with ws=7 or ws=12")
+        return cpu_ops.window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale)
+    if out is None:
+        out = torch.empty((B, H * W, C), dtype=torch.float32, device=qkv.device)
+    elif tuple(out.shape) != (B, H * W, C) or out.dtype != torch.float32 or out.device != qkv.device:
+        raise RuntimeError(f"window_attention: out must be float32 {(B, H * W, C)} on qkv's GPU")
+    with torch.cuda.device(qkv.device):
+        rc = native.lib().dvis_window_attention(native.dev_ptr(qkv, "qkv"), None if qkv_bias is None else native.dev_ptr(qkv_bias, "qkv_bias"),
+                                                native.dev_ptr(bias_table, "bias_table"), native.dev_ptr(out, "out"), B, H, W, heads, d, ws,
+                                                shift, scale, native.stream_ptr(qkv.device))
+    native.check(rc, "dvis_window_attention")
+    return out
+
+
 def vps_argmax(mask_logits_kthw, scores, first_resize_size, img_size, out_hw):
     """Fused panoptic arg-max (see dvis_vps_argmax).  mask_logits_kthw: float32 GPU (K, T, h, w) view whose last two
     dims are contiguous; scores float32 (K,).  Returns ids int32 (T,H,W), conf bool (T,H,W), areas int32 (3, K)."""

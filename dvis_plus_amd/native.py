@@ -170,6 +170,8 @@ SIGNATURES = {
     "dvis_contrastive_items_backward_ws_bytes": (_i64, [_i, _i64, _i]),
     "dvis_contrastive_items_backward": (_i, [_p, _i64, _i, _p, _p, _p, _p, _p, _i, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
                                              _p, _p, _p]),
+    "dvis_window_attention_supported": (_i, [_i, _i]),
+    "dvis_window_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
 }
 
 _lib = None

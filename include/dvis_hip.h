@@ -1003,6 +1003,27 @@ int dvis_contrastive_items_backward(const float *src, int64_t R, int C, const in
                                     const int32_t *arow_item, const float *dots, const float *norms, const float *stats,
                                     const float *grad_reid, const float *grad_aux, float *grad_src, void *ws, void *stream);
 
+/*
+ * Shifted-window attention of the Swin backbone (csrc/window_attention.hip; mask2former/modeling/backbone/swin.py:131-171, 235-295,
+ * 413-440): pad, cyclic shift, window partition, per-head relative-position bias, region mask, softmax, P V, window reverse, reverse
+ * shift and crop in one launch.
+ * qkv (B, H W, 3 C) fp32: the block's qkv projection on the UNPADDED token grid, columns [3][heads][d], C = heads * d;
+ * qkv_bias (3 C) or null; bias_table ((2 ws - 1)^2, heads) raw; out (B, H W, C), columns [heads][d].  qkv, qkv_bias, out 16-byte aligned.
+ * Hp = ceil(H / ws) ws, Wp likewise.  The token at shifted coordinate (ys, xs) comes from source ((ys + shift) % Hp, (xs + shift) %
+ * Wp); a source at or beyond (H, W) is a pad token whose q / k / v is qkv_bias (zeros when null): the reference pads AFTER norm1.
+ * Window (ys / ws, xs / ws) holds N = ws^2 tokens in row-major local order.  score(i, j) = scale q_i . k_j + table[(iy - jy + ws - 1)
+ * (2 ws - 1) + (ix - jx + ws - 1)][head], plus -100 (additive) when shift > 0 and the region ids of i and j differ, region id of a
+ * shifted coordinate = 3 r(ys, Hp) + r(xs, Wp), r(n, N) = (n >= N - ws) + (n >= N - shift).  Softmax over j with the row maximum
+ * subtracted, times v.  Only rows at un-padded source positions are written (each exactly once).  0 <= shift < ws; the shift is
+ * applied even when the map is smaller than one window.
+ * Exact fp32 (v_mfma_f32_16x16x4_f32), no workspace, no atomics, no memset: capturable; the same bits every call, and a frame's
+ * bits do not depend on B.  One frame's qkv must be below 2^31 bytes (per-frame bases are 64-bit).
+ * dvis_window_attention_supported: 1 where (ws, d) is served (d = 32 with ws = 7 or 12); the call refuses every other pair.
+ */
+int dvis_window_attention_supported(int ws, int d);
+int dvis_window_attention(const float *qkv, const float *qkv_bias, const float *bias_table, float *out, int B, int H, int W, int heads,
+                          int d, int ws, int shift, float scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
