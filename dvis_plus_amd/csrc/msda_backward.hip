@@ -365,7 +365,7 @@ DVIS_EXPORT int64_t dvis_msda_fused_backward_ws_bytes(int N, int S, int M, int D
   return dvis_msda_backward_det_ws_bytes(N, S, M, D);
 }
 
-// Backward of dvis_msda_fused_forward (fp32, the reference's row layout: no slots, no head-major value, no position rows).
+// Backward of dvis_msda_fused_forward (fp32).
 // grad_offsets (N * Lq, M * L * P * 2) and grad_logits (N * Lq, M * L * P) are contiguous and the same bits in both forms and
 // from run to run; the reference points get no gradient.  ws == NULL: grad_value through float atomics; otherwise
 // dvis_msda_fused_backward_ws_bytes bytes, 16-byte aligned: the 64-bit fixed-point form (see DetArgs), reproducible.

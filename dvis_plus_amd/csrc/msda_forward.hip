@@ -133,14 +133,6 @@ struct TileMap {
   int tiles_x[kMaxLevels];          // 8-pixel tiles per row of every level
   int h[kMaxLevels], w[kMaxLevels], q0[kMaxLevels];   // map size and first query of every level
   int tiled;                        // the 8 x 8 geometry above is valid (else: QB consecutive queries per workgroup)
-  // FUSED form: floats between two heads' parameters inside a projection row; 0 = the reference's layout (all heads'
-  // offsets, then all heads' logits: L*P*2 and L*P).  "Slots" = [head m: 2LP offsets | LP logits | pad]: a (query, head)
-  // pair then touches ONE contiguous run of its row instead of two (fewer 128-byte lines shared between the 8 XCDs).
-  int off_hs, logit_hs;
-  // `value` is HEAD-MAJOR (M, N, S, D) instead of the reference's (N, S, M, D): a pixel's D channels of one head are
-  // still one 128-byte line, but neighbouring pixels of the head are ADJACENT lines (two x-neighbouring corners = 256
-  // contiguous bytes) instead of M * D * 4 = 1 KB apart — what the value projection writes through dvis_gemm_nt_hm.
-  int value_hm;
 };
 
 bool make_tile_map(const int64_t *shapes_host, int L, int Lq, TileMap *tm) {
@@ -172,7 +164,7 @@ __global__ __launch_bounds__(256, WPS) void msda_fwd_tile(
     const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
     const T *__restrict__ loc_or_off, int64_t off_stride, const T *__restrict__ w_or_logit,
     int64_t logit_stride, const float *__restrict__ refp, int nref, int S, int M, int Lq, T *__restrict__ out,
-    const float *__restrict__ pos_off, const float *__restrict__ pos_logit, int64_t pos_stride, TileMap tm) {
+    TileMap tm) {
   static_assert(!TILE2D || QB == 64, "an 8 x 8 tile per workgroup");
   constexpr int LP = L * P;
   constexpr int CPL = Chan<T>::kPerLane;   // channels per lane (16 bytes)
@@ -227,12 +219,21 @@ __global__ __launch_bounds__(256, WPS) void msda_fwd_tile(
     }
   };
 
+  // ---- per-level buffer descriptors over this (frame, head) slice of `value`: wave-uniform, built BEFORE the set-up so that
+  // the level sizes and starts are not kept alive across it for them
+  __amdgpu_buffer_rsrc_t rs[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const T *base = value + (((size_t)n * S + (size_t)level_start[l]) * M + m) * D;
+    rs[l] = dvis_make_rsrc_uniform(base, (unsigned)(((size_t)(Hs[l] * Ws[l] - 1) * MD + D) * sizeof(T)));
+  }
+
   // ---- set-up: thread (query tid / P, point tid % P) reads ITS parameters of all L levels straight into registers —
   // raw offsets, reference points and the pair's L*P logits (fused) or locations and weights — in ONE global round trip,
   // then softmax, loc = ref + off / (W_l, H_l) and the taps, and ONE barrier.  (The first form staged the rows in LDS,
   // synchronised, loaded the reference points, computed, synchronised again: with the gather switched off that set-up
   // alone took 12.7-15.5 us per 720p frame-layer, and with the loads switched off the kernel still took 23.5 of 35 us.)
-  const unsigned pix_bytes = (unsigned)(tm.value_hm ? D : MD) * (unsigned)sizeof(T);
+  const unsigned pix_bytes = (unsigned)MD * (unsigned)sizeof(T);
   static_assert(QB * P <= 256, "one set-up thread per (query, point)");
   if (tid < QB * P) {
     const int ql = tid / P, p = tid - ql * P;
@@ -242,9 +243,8 @@ __global__ __launch_bounds__(256, WPS) void msda_fwd_tile(
     float2 xy[L];
     float aw[L];
     if constexpr (FUSED) {
-      const int off_hs = tm.off_hs ? tm.off_hs : LP * 2, logit_hs = tm.logit_hs ? tm.logit_hs : LP;
-      const T *orow = loc_or_off + ((size_t)n * Lq + qq) * off_stride + (size_t)m * off_hs;
-      const T *lrow = w_or_logit + ((size_t)n * Lq + qq) * logit_stride + (size_t)m * logit_hs;
+      const T *orow = loc_or_off + ((size_t)n * Lq + qq) * off_stride + (size_t)m * (LP * 2);
+      const T *lrow = w_or_logit + ((size_t)n * Lq + qq) * logit_stride + (size_t)m * LP;
       float2 ro[L], rr[L];
       float4 rl[LP / 4];
 #pragma unroll
@@ -254,20 +254,6 @@ __global__ __launch_bounds__(256, WPS) void msda_fwd_tile(
       }
 #pragma unroll
       for (int k = 0; k < LP / 4; ++k) rl[k] = Chan<T>::load4(lrow + 4 * k);
-      if (pos_off != nullptr) {     // + projection of the query's position embedding (same for all n)
-        const float *prow = pos_off + qq * pos_stride + (size_t)m * off_hs;
-        const float *plrow = pos_logit + qq * pos_stride + (size_t)m * logit_hs;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-          const float2 pv = *reinterpret_cast<const float2 *>(prow + 2 * (l * P + p));
-          ro[l].x += pv.x; ro[l].y += pv.y;
-        }
-#pragma unroll
-        for (int k = 0; k < LP / 4; ++k) {
-          const float4 pv = *reinterpret_cast<const float4 *>(plrow + 4 * k);
-          rl[k].x += pv.x; rl[k].y += pv.y; rl[k].z += pv.z; rl[k].w += pv.w;
-        }
-      }
       float lg[LP];
 #pragma unroll
       for (int k = 0; k < LP / 4; ++k) { lg[4 * k] = rl[k].x; lg[4 * k + 1] = rl[k].y; lg[4 * k + 2] = rl[k].z; lg[4 * k + 3] = rl[k].w; }
@@ -307,17 +293,6 @@ __global__ __launch_bounds__(256, WPS) void msda_fwd_tile(
   }
   __syncthreads();
   const float *wf = s_aw;
-
-  // ---- per-level buffer descriptors over this (frame, head) slice of `value`
-  __amdgpu_buffer_rsrc_t rs[L];
-#pragma unroll
-  for (int l = 0; l < L; ++l) {
-    const T *base = tm.value_hm
-                        ? value + (((size_t)m * gridDim.z + n) * S + (size_t)level_start[l]) * D
-                        : value + (((size_t)n * S + (size_t)level_start[l]) * M + m) * D;
-    rs[l] = dvis_make_rsrc_uniform(
-        base, (unsigned)(((size_t)(Hs[l] * Ws[l] - 1) * (tm.value_hm ? D : MD) + D) * sizeof(T)));
-  }
 
   const int lane = tid & 63, wv = tid >> 6;
   const int g = lane / G, j = lane - g * G;
@@ -436,16 +411,15 @@ int launch_generic(const void *value, const int64_t *shapes, const int64_t *ls, 
 template <typename T, int D, int L, int P, bool FUSED, int WPS, int B, int QB>
 int launch_variant(const T *value, const int64_t *shapes, const int64_t *ls, const T *a, int64_t a_stride,
                    const T *b, int64_t b_stride, const float *refp, int nref, int N, int S, int M, int Lq, T *out,
-                   hipStream_t st, const float *pos_off, const float *pos_logit, int64_t pos_stride, const TileMap *tm) {
-  if constexpr (QB == 64 && L <= kMaxLevels) {
+                   hipStream_t st, const TileMap *tm) {
+  if constexpr (FUSED && QB == 64 && L <= kMaxLevels) {     // (only the fused entries build a TileMap)
     if (tm != nullptr && tm->tiled) {
       if (N > 65535) {
         dvis_set_error("msda: grid too large (N must be <= 65535)");
         return DVIS_E_ARG;
       }
       hipLaunchKernelGGL((msda_fwd_tile<T, D, L, P, FUSED, WPS, B, QB, true>), dim3(M, tm->tile_start[kMaxLevels], N),
-                         dim3(256), 0, st, value, shapes, ls, a, a_stride, b, b_stride, refp, nref, S, M, Lq, out, pos_off,
-                         pos_logit, pos_stride, *tm);
+                         dim3(256), 0, st, value, shapes, ls, a, a_stride, b, b_stride, refp, nref, S, M, Lq, out, *tm);
       return dvis_check_launch("msda_fwd_tile<2-D>");
     }
   }
@@ -455,18 +429,17 @@ int launch_variant(const T *value, const int64_t *shapes, const int64_t *ls, con
     return DVIS_E_ARG;
   }
   hipLaunchKernelGGL((msda_fwd_tile<T, D, L, P, FUSED, WPS, B, QB, false>), dim3(M, nchunks, N), dim3(256), 0, st, value,
-                     shapes, ls, a, a_stride, b, b_stride, refp, nref, S, M, Lq, out, pos_off, pos_logit, pos_stride,
-                     tm ? *tm : TileMap{});
+                     shapes, ls, a, a_stride, b, b_stride, refp, nref, S, M, Lq, out, tm ? *tm : TileMap{});
   return dvis_check_launch("msda_fwd_tile");
 }
 
 template <typename T, int D, int L, int P, bool FUSED>
 int launch_tile(const T *value, const int64_t *shapes, const int64_t *ls, const T *a, int64_t a_stride,
                 const T *b, int64_t b_stride, const float *refp, int nref, int N, int S, int M, int Lq, T *out,
-                hipStream_t st, const float *pos_off, const float *pos_logit, int64_t pos_stride, const TileMap *tm) {
+                hipStream_t st, const TileMap *tm) {
 #define DVIS_LAUNCH_VARIANT(wps, bsz, qb) \
   return launch_variant<T, D, L, P, FUSED, wps, bsz, qb>(value, shapes, ls, a, a_stride, b, b_stride, refp, nref, N, S, M, \
-                                                         Lq, out, st, pos_off, pos_logit, pos_stride, tm)
+                                                         Lq, out, st, tm)
   // queries covered by one pass of the 4 waves (fp32: 16 B = 4 channels per lane), never more than one set-up thread
   // per (query, point) allows
   constexpr int QMIN = 4 * (64 / (D / 4)) < 256 / P / 2 ? 4 * (64 / (D / 4)) : 256 / P / 2;
@@ -480,13 +453,12 @@ int launch_tile(const T *value, const int64_t *shapes, const int64_t *ls, const 
 template <typename T, bool FUSED>
 int dispatch_tile(int D, int L, int P, const T *value, const int64_t *shapes, const int64_t *ls, const T *a,
                   int64_t a_stride, const T *b, int64_t b_stride, const float *refp, int nref, int N, int S, int M,
-                  int Lq, T *out, hipStream_t st, bool *handled, const float *pos_off = nullptr,
-                  const float *pos_logit = nullptr, int64_t pos_stride = 0, const TileMap *tm = nullptr) {
+                  int Lq, T *out, hipStream_t st, bool *handled, const TileMap *tm = nullptr) {
   *handled = true;
 #define DVIS_TILE_CASE(d, l, p)  \
   if (D == d && L == l && P == p) \
     return launch_tile<T, d, l, p, FUSED>(value, shapes, ls, a, a_stride, b, b_stride, refp, nref, N, S, M, Lq, out, st, \
-                                          pos_off, pos_logit, pos_stride, tm);
+                                          tm);
   DVIS_TILE_CASE(32, 3, 4)
   DVIS_TILE_CASE(32, 4, 4)
   DVIS_TILE_CASE(32, 1, 4)
@@ -542,60 +514,49 @@ DVIS_EXPORT int dvis_msda_forward(int dtype, const void *value, const int64_t *s
   return DVIS_E_ARG;
 }
 
-DVIS_EXPORT int dvis_msda_fused_forward_slots(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                              const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                              const float *logits, int64_t logit_stride, int off_head_stride,
-                                              int logit_head_stride, int value_head_major, const float *pos_offsets,
-                                              const float *pos_logits, int64_t pos_stride, int N, int S, int M, int D,
-                                              int L, int Lq, int P, float *out, const int64_t *shapes_host,
-                                              void *stream) {
-  DVIS_REQUIRE(N >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "msda_fused_forward: bad sizes");
+// Host side of the fused form for one storage type T: value, the raw offset / logit rows and the output in T (fp32, or fp16 /
+// bf16 — what nn.Linear hands over under autocast), reference points fp32, all arithmetic fp32.  Rows in the reference's
+// layout (all heads' offsets, then all heads' logits), strides in elements.  `who` names the entry in the error messages.
+template <typename T>
+static int fused_forward(const char *who, const void *value, const int64_t *shapes, const int64_t *level_start,
+                         const float *ref, int Nref, const void *offsets, int64_t off_stride, const void *logits,
+                         int64_t logit_stride, int N, int S, int M, int D, int L, int Lq, int P, void *out,
+                         const int64_t *shapes_host, void *stream) {
+  constexpr bool kF32 = sizeof(T) == 4;
+  DVIS_REQUIRE(N >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "%s: bad sizes", who);
   if (N == 0 || Lq == 0) return DVIS_OK;
-  DVIS_REQUIRE(value && shapes && level_start && ref && offsets && logits && out, "msda_fused_forward: null pointer");
-  DVIS_REQUIRE(Nref == 1 || Nref == N, "msda_fused_forward: Nref must be 1 or N");
-  const int off_hs = off_head_stride ? off_head_stride : L * P * 2, logit_hs = logit_head_stride ? logit_head_stride : L * P;
-  DVIS_REQUIRE(off_hs >= L * P * 2 && logit_hs >= L * P && off_hs % 4 == 0 && logit_hs % 4 == 0,
-               "msda_fused_forward: head strides must cover a head's parameters and be multiples of 4 floats");
-  DVIS_REQUIRE(off_stride >= (int64_t)(M - 1) * off_hs + L * P * 2 && logit_stride >= (int64_t)(M - 1) * logit_hs + L * P,
-               "msda_fused_forward: row strides too small");
-  DVIS_REQUIRE(off_stride % 4 == 0 && logit_stride % 4 == 0 && aligned16(offsets) && aligned16(logits) &&
-                   aligned16(value) && aligned16(out),
-               "msda_fused_forward: 16-byte alignment required");
-  DVIS_REQUIRE((size_t)S * M * D * sizeof(float) < 0x7fffffffu, "msda_fused_forward: frame slice >= 2 GiB");
-  bool handled = false;
-  DVIS_REQUIRE((size_t)Lq * (size_t)(off_stride > logit_stride ? off_stride : logit_stride) * sizeof(float) < 0x7fffffffu,
-               "msda_fused_forward: one frame of offsets/logits must stay below 2 GiB");
+  DVIS_REQUIRE(value && shapes && level_start && ref && offsets && logits && out, "%s: null pointer", who);
+  DVIS_REQUIRE(Nref == 1 || Nref == N, "%s: Nref must be 1 or N", who);
+  DVIS_REQUIRE(off_stride >= (int64_t)M * L * P * 2 && logit_stride >= (int64_t)M * L * P && off_stride % 4 == 0 &&
+                   logit_stride % 4 == 0 && (L * P) % 4 == 0,
+               "%s: row strides must cover the rows (M*L*P*2 / M*L*P) and, like L*P, be multiples of 4 elements", who);
+  // a set-up thread reads 4 logits at once: 16-byte rows in fp32, 8-byte rows in half; a lane gathers 16 bytes of `value`
+  DVIS_REQUIRE((((uintptr_t)offsets | (uintptr_t)logits) & (kF32 ? 15u : 7u)) == 0 && aligned16(value) && aligned16(out) &&
+                   (kF32 || (M * D) % 8 == 0),
+               "%s: %d-byte aligned rows and 16-byte aligned value / out required%s", who, kF32 ? 16 : 8,
+               kF32 ? "" : ", M*D a multiple of 8");
+  DVIS_REQUIRE((size_t)S * M * D * sizeof(T) < 0x7fffffffu, "%s: frame slice >= 2 GiB", who);
+  if constexpr (kF32)     // (the limit dvis_msda_fused_backward shares with its forward)
+    DVIS_REQUIRE((size_t)Lq * (size_t)(off_stride > logit_stride ? off_stride : logit_stride) * sizeof(T) < 0x7fffffffu,
+                 "%s: one frame of offsets/logits must stay below 2 GiB", who);
   // Encoder self-attention geometry (queries = the pixels of the L maps, shapes known on the host): 8 x 8 query tiles
   TileMap tm{};
-  const bool has_pos = pos_offsets != nullptr || pos_logits != nullptr;
-  if (!has_pos) make_tile_map(shapes_host, L, Lq, &tm);
-  tm.off_hs = off_head_stride, tm.logit_hs = logit_head_stride;
-  tm.value_hm = value_head_major ? 1 : 0;
-  if (has_pos) {
-    DVIS_REQUIRE(pos_offsets && pos_logits && pos_stride >= (int64_t)(M - 1) * off_hs + L * P * 2 && pos_stride % 4 == 0 &&
-                     aligned16(pos_offsets) && aligned16(pos_logits),
-                 "msda_fused_forward: position rows need both pointers, 16-byte alignment and a row stride multiple of 4");
-    tm.tiled = 0;
-  }
-  const int rc = dispatch_tile<float, true>(D, L, P, value, shapes, level_start, offsets, off_stride, logits, logit_stride, ref,
-                                            Nref, N, S, M, Lq, out, (hipStream_t)stream, &handled, pos_offsets, pos_logits,
-                                            pos_stride, &tm);
+  make_tile_map(shapes_host, L, Lq, &tm);
+  bool handled = false;
+  const int rc = dispatch_tile<T, true>(D, L, P, (const T *)value, shapes, level_start, (const T *)offsets, off_stride,
+                                        (const T *)logits, logit_stride, ref, Nref, N, S, M, Lq, (T *)out, (hipStream_t)stream,
+                                        &handled, &tm);
   if (handled) return rc;
-  dvis_set_error("msda_fused_forward: unsupported (D=%d, L=%d, P=%d); supported D in {32,64}, (L,P) in {(1,4),(3,4),(4,4)}",
-                 D, L, P);
+  dvis_set_error("%s: unsupported (D=%d, L=%d, P=%d); supported D in {32,64}, (L,P) in {(1,4),(3,4),(4,4)}", who, D, L, P);
   return DVIS_E_UNSUPPORTED;
 }
 
-// The fused form on fp16 / bf16 storage: value, the raw offset / logit rows and the output in `dtype` (what nn.Linear hands
-// over under autocast), reference points fp32, all arithmetic fp32.  The reference's row layout only (no slots / head-major).
-template <typename T>
-static int fused_half(const void *value, const int64_t *shapes, const int64_t *level_start, const float *ref, int Nref,
-                      const void *offsets, int64_t off_stride, const void *logits, int64_t logit_stride, int N, int S, int M, int D,
-                      int L, int Lq, int P, void *out, const int64_t *shapes_host, hipStream_t st, bool *handled) {
-  TileMap tm{};
-  make_tile_map(shapes_host, L, Lq, &tm);
-  return dispatch_tile<T, true>(D, L, P, (const T *)value, shapes, level_start, (const T *)offsets, off_stride, (const T *)logits,
-                                logit_stride, ref, Nref, N, S, M, Lq, (T *)out, st, handled, nullptr, nullptr, 0, &tm);
+DVIS_EXPORT int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int64_t *level_start,
+                                        const float *ref, int Nref, const float *offsets, int64_t off_stride,
+                                        const float *logits, int64_t logit_stride, int N, int S, int M, int D, int L,
+                                        int Lq, int P, float *out, const int64_t *shapes_host, void *stream) {
+  return fused_forward<float>("msda_fused_forward", value, shapes, level_start, ref, Nref, offsets, off_stride, logits,
+                              logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream);
 }
 
 DVIS_EXPORT int dvis_msda_fused_forward_h(int dtype, const void *value, const int64_t *shapes, const int64_t *level_start,
@@ -603,40 +564,9 @@ DVIS_EXPORT int dvis_msda_fused_forward_h(int dtype, const void *value, const in
                                           const void *logits, int64_t logit_stride, int N, int S, int M, int D, int L, int Lq,
                                           int P, void *out, const int64_t *shapes_host, void *stream) {
   DVIS_REQUIRE(dtype == DVIS_F16 || dtype == DVIS_BF16, "msda_fused_forward_h: dtype must be fp16 or bf16 (fp32: dvis_msda_fused_forward)");
-  DVIS_REQUIRE(N >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "msda_fused_forward_h: bad sizes");
-  if (N == 0 || Lq == 0) return DVIS_OK;
-  DVIS_REQUIRE(value && shapes && level_start && ref && offsets && logits && out, "msda_fused_forward_h: null pointer");
-  DVIS_REQUIRE(Nref == 1 || Nref == N, "msda_fused_forward_h: Nref must be 1 or N");
-  DVIS_REQUIRE(off_stride >= (int64_t)M * L * P * 2 && logit_stride >= (int64_t)M * L * P && off_stride % 4 == 0 &&
-                   logit_stride % 4 == 0 && (((uintptr_t)offsets | (uintptr_t)logits) & 7u) == 0 && aligned16(value) &&
-                   aligned16(out) && (M * D) % 8 == 0 && (L * P) % 4 == 0,
-               "msda_fused_forward_h: row strides must cover the rows and be multiples of 4 elements; 8-byte aligned rows, "
-               "16-byte aligned value / out");
-  DVIS_REQUIRE((size_t)S * M * D * 2 < 0x7fffffffu, "msda_fused_forward_h: frame slice >= 2 GiB");
-  bool handled = false;
-  const int rc = dtype == DVIS_F16
-                     ? fused_half<__half>(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride, N, S, M,
-                                          D, L, Lq, P, out, shapes_host, (hipStream_t)stream, &handled)
-                     : fused_half<__hip_bfloat16>(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride,
-                                                  N, S, M, D, L, Lq, P, out, shapes_host, (hipStream_t)stream, &handled);
-  if (handled) return rc;
-  dvis_set_error("msda_fused_forward_h: unsupported (D=%d, L=%d, P=%d); supported D in {32,64}, (L,P) in {(1,4),(3,4),(4,4)}", D, L, P);
-  return DVIS_E_UNSUPPORTED;
-}
-
-DVIS_EXPORT int dvis_msda_fused_forward_pos(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                            const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                            const float *logits, int64_t logit_stride, const float *pos_offsets,
-                                            const float *pos_logits, int64_t pos_stride, int N, int S, int M, int D,
-                                            int L, int Lq, int P, float *out, const int64_t *shapes_host, void *stream) {
-  return dvis_msda_fused_forward_slots(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride, 0, 0,
-                                       0, pos_offsets, pos_logits, pos_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream);
-}
-
-DVIS_EXPORT int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                        const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                        const float *logits, int64_t logit_stride, int N, int S, int M, int D, int L,
-                                        int Lq, int P, float *out, const int64_t *shapes_host, void *stream) {
-  return dvis_msda_fused_forward_pos(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride,
-                                     nullptr, nullptr, 0, N, S, M, D, L, Lq, P, out, shapes_host, stream);
+  return dtype == DVIS_F16
+             ? fused_forward<__half>("msda_fused_forward_h", value, shapes, level_start, ref, Nref, offsets, off_stride, logits,
+                                     logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream)
+             : fused_forward<__hip_bfloat16>("msda_fused_forward_h", value, shapes, level_start, ref, Nref, offsets, off_stride,
+                                             logits, logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream);
 }

@@ -174,8 +174,7 @@ class MSDeformAttnFunction(Function):
 
 
 def msda_fused_forward(value, spatial_shapes, level_start_index, reference_points, offsets, logits, n_levels,
-                       n_points, shapes_host=None, pos_offsets=None, pos_logits=None, head_stride=0,
-                       value_head_major=False):
+                       n_points, shapes_host=None):
     """Inference fast path of ``MSDeformAttn.forward`` (ops/modules/ms_deform_attn.py:101-117): fp32, or fp16 / bf16
     storage with fp32 arithmetic (value, offsets, logits and the output in ONE dtype — the module under autocast).
 
@@ -183,77 +182,35 @@ def msda_fused_forward(value, spatial_shapes, level_start_index, reference_point
     (N*Lq, >= M*L*P*2) / (N*Lq, >= M*L*P) of the raw linear outputs (row stride may exceed the width, e.g.
     both sliced out of one fused projection).  softmax + location arithmetic happen inside the kernel.
     shapes_host: optional [(H, W), ...] python copy of spatial_shapes (enables 8x8 query tiling for self-attention).
-    pos_offsets / pos_logits: optional (Lq, >= M*L*P*2) / (Lq, >= M*L*P) row views with the SAME row stride: the
-    bias-free projections of the queries' position embedding, added to the raw rows inside the kernel
-    (linear(src + pos) = linear(src) + pos W^T), so the caller projects `src` and never forms `src + pos`.
-    head_stride: 0 = the reference's row layout (all heads' offsets, then all heads' logits); s > 0 = per-head SLOTS of s
-    floats [2LP offsets | LP logits | pad]: `offsets` then points at a row's first slot and `logits` 2LP floats further.
-    value_head_major: `value` is (M, N, S, D) — head outermost — instead of (N, S, M, D).
     """
-    if value_head_major:            # (M, N, S, D): head outermost (gemm_nt(head_major=D) of the value projection)
-        M, N, S, D = value.shape
-    else:
-        N, S, M, D = value.shape
+    N, S, M, D = value.shape
     L, P = n_levels, n_points
     nref, Lq = reference_points.shape[0], reference_points.shape[1]
     for name, t in (("value", value), ("reference_points", reference_points)):
         native.dev_ptr(t, name)
-    half = value.dtype in (torch.float16, torch.bfloat16)
     for name, t in (("offsets", offsets), ("logits", logits)):
         if not t.is_cuda or t.dtype != value.dtype or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != N * Lq:
             raise RuntimeError(f"{name} must be a GPU (N*Lq, width) row view of value's dtype with unit inner stride")
     if value.dtype not in (torch.float32, torch.float16, torch.bfloat16) or reference_points.dtype != torch.float32:
         raise RuntimeError("msda_fused_forward: value / offsets / logits fp32, fp16 or bf16 (one dtype); reference points fp32")
-    if half:
-        # fp16 / bf16 storage (what the projections produce under autocast), fp32 arithmetic: dvis_msda_fused_forward_h
-        if head_stride or value_head_major or pos_offsets is not None or pos_logits is not None:
-            raise RuntimeError("msda_fused_forward: slots / head-major value / position rows are fp32-only layouts")
-        if offsets.shape[1] < M * L * P * 2 or logits.shape[1] < M * L * P or reference_points.shape[2:] != (L, 2):
-            raise RuntimeError("msda_fused_forward: inconsistent shapes")
-        out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
-        hs = None
-        if shapes_host is not None:
-            hs = (ctypes.c_int64 * (2 * L))(*[int(v) for hw in shapes_host for v in hw])
-        with torch.cuda.device(value.device):
-            rc = native.lib().dvis_msda_fused_forward_h(
-                native.dtype_code(value), native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
-                native.dev_ptr(level_start_index, "level_start_index"), native.dev_ptr(reference_points, "ref"), nref,
-                ctypes.c_void_p(offsets.data_ptr()), offsets.stride(0), ctypes.c_void_p(logits.data_ptr()), logits.stride(0),
-                N, S, M, D, L, Lq, P, native.dev_ptr(out, "out"), hs, native.stream_ptr(value.device))
-        native.check(rc, "dvis_msda_fused_forward_h")
-        return out
-    if head_stride:
-        if offsets.shape[1] < (M - 1) * head_stride + L * P * 2 or logits.shape[1] < (M - 1) * head_stride + L * P:
-            raise RuntimeError("msda_fused_forward: rows shorter than M slots")
-    elif offsets.shape[1] < M * L * P * 2 or logits.shape[1] < M * L * P:
-        raise RuntimeError("msda_fused_forward: inconsistent shapes")
-    if reference_points.shape[2:] != (L, 2):
+    if offsets.shape[1] < M * L * P * 2 or logits.shape[1] < M * L * P or reference_points.shape[2:] != (L, 2):
         raise RuntimeError("msda_fused_forward: inconsistent shapes")
     out = torch.empty((N, Lq, M * D), dtype=value.dtype, device=value.device)
     hs = None
     if shapes_host is not None:
         hs = (ctypes.c_int64 * (2 * L))(*[int(v) for hw in shapes_host for v in hw])
-    po = pl = None
-    pstride = 0
-    if pos_offsets is not None or pos_logits is not None:
-        wo = (M - 1) * head_stride + L * P * 2 if head_stride else M * L * P * 2
-        wl = (M - 1) * head_stride + L * P if head_stride else M * L * P
-        for name, t, width in (("pos_offsets", pos_offsets, wo), ("pos_logits", pos_logits, wl)):
-            if t is None or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 \
-                    or t.shape[0] != Lq or t.shape[1] < width:
-                raise RuntimeError(f"{name} must be a float32 GPU (Lq, >= {width}) row view with unit inner stride")
-        if pos_offsets.stride(0) != pos_logits.stride(0):
-            raise RuntimeError("pos_offsets / pos_logits must share their row stride (slices of one projection)")
-        po, pl, pstride = ctypes.c_void_p(pos_offsets.data_ptr()), ctypes.c_void_p(pos_logits.data_ptr()), pos_offsets.stride(0)
+    # fp16 / bf16 storage (what the projections produce under autocast) has an entry of its own, led by the dtype code
+    if value.dtype == torch.float32:
+        entry, lead = "dvis_msda_fused_forward", ()
+    else:
+        entry, lead = "dvis_msda_fused_forward_h", (native.dtype_code(value),)
     with torch.cuda.device(value.device):
-        rc = native.lib().dvis_msda_fused_forward_slots(
-            native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
+        rc = getattr(native.lib(), entry)(
+            *lead, native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
             native.dev_ptr(level_start_index, "level_start_index"), native.dev_ptr(reference_points, "ref"), nref,
-            ctypes.c_void_p(offsets.data_ptr()), offsets.stride(0), ctypes.c_void_p(logits.data_ptr()),
-            logits.stride(0), int(head_stride), int(head_stride), 1 if value_head_major else 0, po, pl, pstride,
-            N, S, M, D, L, Lq, P,
-            native.dev_ptr(out, "out"), hs, native.stream_ptr(value.device))
-    native.check(rc, "dvis_msda_fused_forward")
+            ctypes.c_void_p(offsets.data_ptr()), offsets.stride(0), ctypes.c_void_p(logits.data_ptr()), logits.stride(0),
+            N, S, M, D, L, Lq, P, native.dev_ptr(out, "out"), hs, native.stream_ptr(value.device))
+    native.check(rc, entry)
     return out
 
 
@@ -266,8 +223,8 @@ def msda_fused_backward_ok(x, head_dim, n_levels, n_points):
 
 def msda_fused_backward(value, spatial_shapes, level_start_index, reference_points, offsets, logits, grad_out, n_levels,
                         n_points, deterministic=None):
-    """Backward of ``msda_fused_forward`` in its fp32 domain (D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, no slots / head-major
-    value / position rows) -> (grad_value (N,S,M,D), grad_offsets (N*Lq, M*L*P*2), grad_logits (N*Lq, M*L*P)).  The inputs are
+    """Backward of ``msda_fused_forward`` in its fp32 domain (D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)})
+    -> (grad_value (N,S,M,D), grad_offsets (N*Lq, M*L*P*2), grad_logits (N*Lq, M*L*P)).  The inputs are
     the forward's own — the RAW row views — and the kernel recomputes softmax and locations: no (N, Lq, M, L, P, 3) tensor is
     read or written.  The reference points get no gradient.  deterministic: as ``ms_deform_attn_backward`` (grad_offsets /
     grad_logits are the same bits either way)."""
@@ -1321,13 +1278,11 @@ def _rows2d(x, K):
     return x.view(-1, K), K
 
 
-def gemm_nt(a, w, bias=None, relu=False, res=None, config=-1, head_major=0, out=None):
+def gemm_nt(a, w, bias=None, relu=False, res=None, config=-1, out=None):
     """``relu?(a @ w.T + bias + res)`` on the deterministic exact-fp32 MFMA kernel (dvis_gemm_nt).  a (..., K) float32 GPU
     tensor (rows with unit inner stride; a row-sliced 2-D view keeps its row stride), w (N, K) in F.linear's layout (row
     stride >= K allowed), bias (N) or None, res (..., N) or None.  Returns (..., N).  Raises when the kernel cannot serve
-    the operands (K or a row stride not a multiple of 4, unaligned base) — there is no silent library fallback here.
-    head_major = d > 0: the output is written as (N / d, M, d) — N / d matrices of M rows, d columns each (the head-major
-    value layout of MSDeformAttn) — and returned with that shape (M = all leading dims of `a` flattened)."""
+    the operands (K or a row stride not a multiple of 4, unaligned base) — there is no silent library fallback here."""
     K = a.shape[-1]
     N = w.shape[0]
     if not (a.is_cuda and a.dtype == torch.float32 and w.dtype == torch.float32 and w.dim() == 2 and w.shape[1] == K
@@ -1335,11 +1290,7 @@ def gemm_nt(a, w, bias=None, relu=False, res=None, config=-1, head_major=0, out=
         raise RuntimeError("gemm_nt: needs float32 GPU operands a (..., K), w (N, K) with unit inner strides")
     a2, lda = _rows2d(a, K)
     M = a2.shape[0]
-    if head_major:
-        if N % head_major or head_major % 4 or res is not None:
-            raise RuntimeError("gemm_nt: head_major needs N % d == 0, d % 4 == 0 and no residual")
-        out = torch.empty((N // head_major, M, head_major), dtype=torch.float32, device=a.device)
-    elif out is None:
+    if out is None:
         out = torch.empty((*a.shape[:-1], N), dtype=torch.float32, device=a.device)
     elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == M * N):
         raise RuntimeError("gemm_nt: out must be a contiguous float32 GPU tensor of M * N elements")
@@ -1355,10 +1306,9 @@ def gemm_nt(a, w, bias=None, relu=False, res=None, config=-1, head_major=0, out=
             raise RuntimeError("gemm_nt: bias must be a contiguous float32 (N,) tensor")
         bp = ctypes.c_void_p(bias.data_ptr())
     with torch.cuda.device(a.device):
-        rc = native.lib().dvis_gemm_nt_hm(ctypes.c_void_p(a2.data_ptr()), lda, 0, ctypes.c_void_p(w.data_ptr()), w.stride(0), 0,
-                                          bp, rp, ldres, 0, ctypes.c_void_p(out.data_ptr()), head_major or N, 0, M, N, K, 1,
-                                          1 if relu else 0, _gemm_config(M, N, K, 1, config), int(head_major),
-                                          M * head_major, native.stream_ptr(a.device))
+        rc = native.lib().dvis_gemm_nt(ctypes.c_void_p(a2.data_ptr()), lda, 0, ctypes.c_void_p(w.data_ptr()), w.stride(0), 0,
+                                       bp, rp, ldres, 0, ctypes.c_void_p(out.data_ptr()), N, 0, M, N, K, 1,
+                                       1 if relu else 0, _gemm_config(M, N, K, 1, config), native.stream_ptr(a.device))
     native.check(rc, "dvis_gemm_nt")
     return out
 

@@ -29,11 +29,7 @@ SIGNATURES = {
     "dvis_msda_fused_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_msda_fused_backward": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dvis_msda_fused_forward": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "dvis_msda_fused_forward_pos": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i,
-                                         _p, _p, _p]),
     "dvis_msda_fused_forward_h": (_i, [_i, _p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "dvis_msda_fused_forward_slots": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _p, _p, _i64, _i, _i, _i, _i,
-                                           _i, _i, _i, _p, _p, _p]),
     "dvis_nchw_to_tokens": (_i, [_p, _p, _i64, _i, _i64, _i64, _i64, _p]),
     "dvis_tokens_to_nchw": (_i, [_p, _p, _i64, _i, _i64, _i64, _i64, _p]),
     "dvis_normalize_pad": (_i, [_p, _i, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
@@ -90,8 +86,6 @@ SIGNATURES = {
     "dvis_lsap_solve": (_i, [_p, _i, _i, _p]),
     "dvis_match_chain": (_i, [_p, _i, _i, _p]),
     "dvis_gemm_nt": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _i, _i, _i, _p]),
-    "dvis_gemm_nt_hm": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _i, _i, _i, _i,
-                             _i64, _p]),
     "dvis_gemm_nt_bb": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64, _p, _i64, _i64, _i, _i, _i, _i, _i, _i,
                              _p]),
     "dvis_gemm_ln": (_i, [_p, _i64, _p, _i64, _p, _p, _f, _p, _p, _f, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _i, _i, _i,

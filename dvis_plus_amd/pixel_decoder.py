@@ -19,7 +19,6 @@ What is different (MI355X-first, same numbers):
   * sine position embeddings and encoder reference points depend on shapes only and are cached per shape.
 """
 import math
-import os
 import warnings
 
 import torch
@@ -30,17 +29,6 @@ from torch.nn.init import constant_, normal_, xavier_uniform_
 from . import derived, functions as Fn
 from .d2 import configurable
 from .registry import SEM_SEG_HEADS_REGISTRY, ShapeSpec
-
-# DVIS_MSDA_POS=1: add the position embedding's projection inside the MSDA kernel instead of forming src + pos.  Measured
-# on MI355X (T=30, 720p): end to end 180.5 vs 179.1 frames/s (+0.8 %), but the MSDA launch itself 1168 vs 1059 us (its
-# set-up phase reads 22 MB more through scattered 16-byte loads) — a wash, so the plain form stays the default.
-_POS_IN_KERNEL = os.environ.get("DVIS_MSDA_POS", "0") == "1"
-# rows of the fused offsets | logits projection permuted into per-head slots (MSDeformAttn._fused_projection)
-# 1: slot = [2LP offsets | LP logits | pad]; 2: slot = [LP logits | 2LP offsets | pad] (the logits 16-byte aligned at the slot
-# start — round 4's probe of round 3's "+6 %": profiles/r04_msda_slot_orders.txt)
-_MSDA_SLOTS = int(os.environ.get("DVIS_MSDA_SLOTS", "0") or 0)
-# the value projection written HEAD-MAJOR (M, N, S, D) by the own GEMM's epilogue and gathered from that layout
-_MSDA_HM = os.environ.get("DVIS_MSDA_HM", "0") == "1"
 
 
 def _is_power_of_2(n):
@@ -99,7 +87,7 @@ class MSDeformAttn(nn.Module):
         self.attention_weights = nn.Linear(d_model, n_heads * n_levels * n_points)
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
-        self._fused = derived.Derived()  # (W_cat, b_cat, head_stride, the two without zero rows) for the inference fast path
+        self._fused = derived.Derived()  # (W_cat, b_cat, the two without zero rows) for the inference fast path
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -122,39 +110,23 @@ class MSDeformAttn(nn.Module):
                 proj.bias.zero_()
 
     def _fused_projection(self):
-        """-> (weight, bias, head_stride, weight / bias without the zero rows) of the ONE GEMM that produces offsets and logits.  head_stride 0: rows in the
-        reference's order [all offsets | all logits | zero rows up to a multiple of 64]; head_stride s: per-head slots
-        [head m: 2LP offset rows | LP logit rows | zero rows] of s = (padded width) / M output columns — the same GEMM
-        width (8 heads x 36 = 288 -> 320 = 8 x 40), but a (query, head) pair's parameters are one contiguous 160-byte run."""
+        """-> (weight, bias, weight / bias without the zero rows) of the ONE GEMM that produces offsets and logits: rows in
+        the reference's order [all offsets | all logits | zero rows up to a multiple of 64]."""
         so, aw = self.sampling_offsets, self.attention_weights
 
         def make():
-            M, LP = self.n_heads, self.n_levels * self.n_points
-            width = -(-(3 * M * LP) // 64) * 64
+            rows = 3 * self.n_heads * self.n_levels * self.n_points
             # zero rows up to a multiple of 64 output columns: the library's GEMM for (579 600 x 256) x (256 x 288) runs
             # at 97 TFLOP/s, for 320 columns at 118 (974 -> 829 us per encoder layer at 30 frames of 720p)
-            slot = width // M if _MSDA_SLOTS and width % M == 0 and (width // M) % 4 == 0 and width // M >= 3 * LP else 0
-            if slot:
-                C = so.weight.shape[1]
-                w = so.weight.new_zeros(M, slot, C)
-                b = so.bias.new_zeros(M, slot)
-                o0, l0 = (LP, 0) if _MSDA_SLOTS == 2 else (0, 2 * LP)       # where the offsets / the logits start in a slot
-                w[:, o0:o0 + 2 * LP] = so.weight.detach().view(M, 2 * LP, C)
-                w[:, l0:l0 + LP] = aw.weight.detach().view(M, LP, C)
-                b[:, o0:o0 + 2 * LP] = so.bias.detach().view(M, 2 * LP)
-                b[:, l0:l0 + LP] = aw.bias.detach().view(M, LP)
-                w, b = w.view(M * slot, C), b.view(M * slot)
-            else:
-                w = torch.cat([so.weight.detach(), aw.weight.detach()], 0)
-                b = torch.cat([so.bias.detach(), aw.bias.detach()], 0)
-                pad = width - w.shape[0]
-                if pad:
-                    w = torch.cat([w, w.new_zeros(pad, w.shape[1])], 0)
-                    b = torch.cat([b, b.new_zeros(pad)], 0)
+            pad = -(-rows // 64) * 64 - rows
+            w = torch.cat([so.weight.detach(), aw.weight.detach()], 0)
+            b = torch.cat([so.bias.detach(), aw.bias.detach()], 0)
+            if pad:
+                w = torch.cat([w, w.new_zeros(pad, w.shape[1])], 0)
+                b = torch.cat([b, b.new_zeros(pad)], 0)
             w, b = w.contiguous(), b.contiguous()
-            rows = w.shape[0] if slot else 3 * M * LP
-            return w, b, slot, w[:rows], b[:rows]       # [3:]: without the zero rows (csrc/gemm_x3.hip needs none)
-        return self._fused.get([so.weight, so.bias, aw.weight, aw.bias], make, (_MSDA_SLOTS,))
+            return w, b, w[:rows], b[:rows]       # [2:]: without the zero rows (csrc/gemm_x3.hip needs none)
+        return self._fused.get([so.weight, so.bias, aw.weight, aw.bias], make)
 
     def _fast_path_ok(self, query, reference_points, input_padding_mask):
         d = self.d_model // self.n_heads
@@ -172,8 +144,8 @@ class MSDeformAttn(nn.Module):
         queries are the pixels themselves (encoder self-attention) it lets the kernel give each block an 8x8 pixel
         tile (cache locality); results do not depend on it.
         `query_pos` (second extra): when given, `query` is the query WITHOUT its position embedding ((1, Lq, C), shared by
-        the batch); the fast path projects it once (bias-free) and the kernel adds it to the projected rows, so the
-        (N, Lq, C) sum `query + query_pos` is never formed.  Other paths add it up front."""
+        the batch); where the split-f16 projection serves it, the sum is formed inside that kernel (dvis_x3_linear_add), so
+        the (N, Lq, C) tensor `query + query_pos` is never written.  Other paths add it up front."""
         if post is not None:
             out = self._forward(query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
                                 input_padding_mask, spatial_shapes_py, query_pos, post)
@@ -192,38 +164,26 @@ class MSDeformAttn(nn.Module):
         fast = self._fast_path_ok(query, reference_points, input_padding_mask)
         # half-precision storage (a .half() / .bfloat16() module, or fp32 parameters under torch.autocast — how the reference
         # evaluates, train_net_video.py:259): the projections come out in fp16 / bf16 and the fused kernel takes them as they
-        # are (dvis_msda_fused_forward_h); the layout experiments below are fp32-only
+        # are (dvis_msda_fused_forward_h)
         lowp = query.dtype != torch.float32 or torch.is_autocast_enabled()
-        hm = fast and _MSDA_HM and input_flatten.is_contiguous() and not lowp
         # the tall projections on the F16 matrix cores with split fp32 operands (csrc/gemm_x3.hip)
-        x3 = fast and Fn.x3_on() and not lowp and not hm and not _MSDA_SLOTS and Fn.x3_ok(input_flatten, self.d_model, self.d_model) \
+        x3 = fast and Fn.x3_on() and not lowp and Fn.x3_ok(input_flatten, self.d_model, self.d_model) \
             and Fn.x3_ok(query, 3 * M * L * P, self.d_model)
         if x3:
             # (Fn.linear: the tiled split-f16 kernel from K = 512 on — the ViT-Adapter extractors' d_model = 1024 — else the streaming one)
             value = Fn.linear(input_flatten, self.value_proj.weight, self.value_proj.bias, tall=True).view(N, Len_in, M, -1)
-        elif hm:
-            # own GEMM with a head-major epilogue: value[m, n, s, :] — neighbouring pixels of a head are adjacent lines
-            value = Fn.gemm_nt(input_flatten.view(N * Len_in, self.d_model), self.value_proj.weight.detach(),
-                               self.value_proj.bias.detach(), head_major=self.d_model // M).view(M, N, Len_in, -1)
         else:
             value = Fn.linear(input_flatten, self.value_proj.weight, self.value_proj.bias, tall=True)   # exact own GEMM (one-wave family)
             if input_padding_mask is not None:
                 value = value.masked_fill(input_padding_mask[..., None], float(0))
             value = value.view(N, Len_in, M, self.d_model // M)
         if fast:
-            w, b, slot, w_rows, b_rows = self._fused_projection()
-            # where a row's offsets / logits start (slots: inside the head's slot)
-            o_off, l_off = ((L * P, 0) if _MSDA_SLOTS == 2 else (0, 2 * L * P)) if slot else (0, M * L * P * 2)
-            po = pl = None
-            if lowp and slot:
-                raise RuntimeError("DVIS_MSDA_SLOTS is an fp32-only layout experiment")
-            if query_pos is not None and query_pos.shape[0] == 1 and _POS_IN_KERNEL and not lowp:
-                pp = Fn.linear(query_pos[0], w)                                    # (Lq, 3*M*L*P): tiny, once per call
-                po, pl = pp[:, o_off:], pp[:, l_off:]
-            elif query_pos is not None and not (x3 and query_pos.shape[0] == 1 and query.dim() == 3 and self.d_model == 256):
+            w, b, w_rows, b_rows = self._fused_projection()
+            o_off, l_off = 0, M * L * P * 2      # where a row's offsets / logits start
+            if query_pos is not None and not (x3 and query_pos.shape[0] == 1 and query.dim() == 3 and self.d_model == 256):
                 query = query + query_pos
                 query_pos = None
-            if x3 and query_pos is not None and po is None:
+            if x3 and query_pos is not None:
                 # `with_pos_embed(src, pos)` inside the projection kernel: the (N, Lq, C) sum is never written
                 proj = Fn.x3_linear(query, w_rows, b_rows, xadd=query_pos).view(N * Len_q, -1)
             elif x3:
@@ -232,15 +192,12 @@ class MSDeformAttn(nn.Module):
                 proj = Fn.linear(query.reshape(N * Len_q, self.d_model), w, b, tall=True)     # offsets | logits in one GEMM
             ref = reference_points if reference_points.is_contiguous() else reference_points.contiguous()
             output = Fn.msda_fused_forward(value, input_spatial_shapes, input_level_start_index, ref,
-                                           proj[:, o_off:], proj[:, l_off:], L, P, shapes_host=spatial_shapes_py,
-                                           pos_offsets=po, pos_logits=pl, head_stride=slot, value_head_major=hm)
+                                           proj[:, o_off:], proj[:, l_off:], L, P, shapes_host=spatial_shapes_py)
             if x3 and post is not None and post[1] is None and post[0].shape[:-1] == output.shape[:-1] and post[0].dtype == torch.float32:
                 return (Fn.linear(output, self.output_proj.weight, self.output_proj.bias, tall=True, residual=post[0]),)
             if x3 and post is not None and post[1] is not None and Fn.x3_ok(output, self.d_model, self.d_model, ln=True) \
                     and post[0].shape == output.shape and post[0].dtype == torch.float32 and post[1].weight is not None:
                 return (Fn.x3_linear_ln(output, self.output_proj.weight, self.output_proj.bias, post[0], post[1]),)
-            if x3:
-                return Fn.linear(output, self.output_proj.weight, self.output_proj.bias, tall=True)
             return Fn.linear(output, self.output_proj.weight, self.output_proj.bias, tall=True)
         if query_pos is not None:
             query = query + query_pos
@@ -306,7 +263,7 @@ class MSDeformAttnTransformerEncoderLayer(nn.Module):
         a = self.self_attn
         return bool(Fn.x3_on() and pos is not None and pos.dim() == 3 and pos.shape[0] == 1 and src.dim() == 3 and src.is_cuda
                     and src.dtype == torch.float32 and not torch.is_grad_enabled() and not torch.is_autocast_enabled()
-                    and not _POS_IN_KERNEL and not _MSDA_SLOTS and not _MSDA_HM and a.d_model == 256
+                    and a.d_model == 256
                     and 3 * a.n_heads * a.n_levels * a.n_points in (128, 192, 256, 288) and a.d_model // a.n_heads in (32, 64)
                     and (a.n_levels, a.n_points) in ((1, 4), (3, 4), (4, 4)))
 

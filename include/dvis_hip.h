@@ -160,8 +160,7 @@ int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int
                             const int64_t *shapes_host, void *stream);
 
 /*
- * Backward of dvis_msda_fused_forward (fp32; the reference's row layout only: no slots, no head-major value, no position rows;
- * D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, the forward's stride / alignment / 2 GiB requirements, Nref in {1, N} — anything
+ * Backward of dvis_msda_fused_forward (fp32; D in {32, 64}, (L, P) in {(1,4), (3,4), (4,4)}, the forward's stride / alignment / 2 GiB requirements, Nref in {1, N} — anything
  * else is an error code before a launch).  Inputs are the forward's own plus grad_out (N, Lq, M*D) contiguous; the kernel recomputes
  * the softmax and the sampling locations per (n, q, m), so neither they nor their gradients exist in memory.
  *   grad_value   (N, S, M, D), fully written by the call
@@ -179,19 +178,6 @@ int dvis_msda_fused_backward(const float *value, const int64_t *shapes, const in
                              float *grad_offsets, float *grad_logits, void *ws, void *stream);
 
 /*
- * Same, plus the projection of the queries' POSITION embedding: MSDeformAttn is called with query = src + pos
- * (pixel_decoder/msdeformattn.py:124-126) and only the two linears above read the query, so
- * linear(src + pos) = linear(src) + (pos W^T).  pos_offsets / pos_logits: one row per QUERY (shared by all N frames,
- * row stride `pos_stride` floats) of (pos W_off^T) / (pos W_logit^T) WITHOUT bias; added to the raw rows inside the
- * kernel — the (N, Lq, C) `src + pos` tensor is never formed.  Both NULL = dvis_msda_fused_forward.
- */
-int dvis_msda_fused_forward_pos(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                const float *logits, int64_t logit_stride, const float *pos_offsets,
-                                const float *pos_logits, int64_t pos_stride, int N, int S, int M, int D, int L, int Lq,
-                                int P, float *out, const int64_t *shapes_host, void *stream);
-
-/*
  * dvis_msda_fused_forward on HALF-PRECISION storage: `value`, the raw offset / logit rows and `out` in `dtype` (DVIS_F16 /
  * DVIS_BF16 — what the projections of MSDeformAttn.forward, ops/modules/ms_deform_attn.py:97-105, produce under
  * torch.autocast, how the reference evaluates: train_net_video.py:259), reference points fp32, arithmetic fp32, 8 channels
@@ -202,22 +188,6 @@ int dvis_msda_fused_forward_h(int dtype, const void *value, const int64_t *shape
                               const float *ref, int Nref, const void *offsets, int64_t off_stride, const void *logits,
                               int64_t logit_stride, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                               const int64_t *shapes_host, void *stream);
-
-/*
- * Same, with the per-head layout of a projection row made explicit: head m's 2*L*P offsets start `off_head_stride` floats
- * after head m-1's, its L*P logits `logit_head_stride` floats after head m-1's (0 = the reference's layout: L*P*2 and
- * L*P, i.e. all heads' offsets, then all heads' logits).  With the rows of the fused projection permuted into per-head
- * SLOTS [2LP offsets | LP logits | pad] (offsets = proj, logits = proj + 2LP, both head strides = the slot size) a
- * (query, head) pair reads one contiguous run of its row: fewer 128-byte lines shared between the heads' XCDs.
- * value_head_major != 0: `value` is laid out (M, N, S, D) — head outermost, as dvis_gemm_nt_hm writes the value projection —
- * instead of the reference's (N, S, M, D): neighbouring pixels of a head are adjacent 128-byte lines.
- */
-int dvis_msda_fused_forward_slots(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                  const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                  const float *logits, int64_t logit_stride, int off_head_stride, int logit_head_stride,
-                                  int value_head_major, const float *pos_offsets, const float *pos_logits, int64_t pos_stride, int N, int S,
-                                  int M, int D, int L, int Lq, int P, float *out, const int64_t *shapes_host,
-                                  void *stream);
 
 /*
  * Mask logits: out[b, q, p] = sum_c embed[b, q, c] * feat[b, c, p]     (fp32, exact-fp32 MFMA)
@@ -622,14 +592,6 @@ int dvis_match_chain(const float *cost, int T, int Q, int64_t *indices);
 int dvis_gemm_nt(const float *A, int64_t lda, int64_t strideA, const float *W, int64_t ldw, int64_t strideW,
                  const float *bias, const float *res, int64_t ldres, int64_t strideRes, float *C, int64_t ldc,
                  int64_t strideC, int M, int N, int K, int batch, int act, int config, void *stream);
-/* Same with a HEAD-MAJOR output: column n of row m is stored at C[(n / head_d) * head_stride + m * head_d + n % head_d], i.e. C
- * is (N / head_d) matrices of M x head_d — the value layout dvis_msda_fused_forward_slots(value_head_major = 1) gathers from
- * (the value projection of MSDeformAttn, ops/modules/ms_deform_attn.py:97-100, written in the layout its consumer wants).
- * head_d == 0: dvis_gemm_nt.  Needs batch == 1, no residual. */
-int dvis_gemm_nt_hm(const float *A, int64_t lda, int64_t strideA, const float *W, int64_t ldw, int64_t strideW,
-                    const float *bias, const float *res, int64_t ldres, int64_t strideRes, float *C, int64_t ldc,
-                    int64_t strideC, int M, int N, int K, int batch, int act, int config, int head_d, int64_t head_stride,
-                    void *stream);
 /* Same as dvis_gemm_nt with a bias PER BATCH ENTRY (strideBias floats apart; 0 = dvis_gemm_nt): `batch` projections with
  * their own weights and biases as one launch — the out-projections of the referring tracker's six cross-attention layers,
  * whose attention does not depend on the layer chain (dvis_Plus/tracker.py:293-318: q = reference, k / v = the frame's queries

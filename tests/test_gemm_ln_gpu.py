@@ -200,7 +200,7 @@ def test_tracker_chain_is_36_launches_per_frame():
     fe_nn = torch.randn(1, 512, 2 * T, Q, generator=g).to(DEV)
     fe = torch.nn.functional.layer_norm(fe_nn.permute(0, 2, 3, 1), (512,)).permute(0, 3, 1, 2).contiguous()
     lib = native.lib()
-    names = ("dvis_gemm_ln", "dvis_gemm_nt", "dvis_gemm_nt_hm", "dvis_gemm_nt_bb", "dvis_attention_forward_k", "dvis_add_layernorm")
+    names = ("dvis_gemm_ln", "dvis_gemm_nt", "dvis_gemm_nt_bb", "dvis_attention_forward_k", "dvis_add_layernorm")
     orig = {n: getattr(lib, n) for n in names}
     counts = {}
 
@@ -231,7 +231,7 @@ def test_tracker_chain_is_36_launches_per_frame():
             trk._recurrence = rec
             per_frame[fused] = (sum(inside.values()) - 1 - (1 if fused else 0)) / T       # minus the K / V GEMM (and the final LN)
             if fused:
-                assert inside == {"dvis_gemm_nt_hm": 1 + T, "dvis_gemm_ln": T * (3 + 6 * 4), "dvis_gemm_nt_bb": T,
+                assert inside == {"dvis_gemm_nt": 1 + T, "dvis_gemm_ln": T * (3 + 6 * 4), "dvis_gemm_nt_bb": T,
                                   "dvis_attention_forward_k": T * 7, "dvis_add_layernorm": 1}, inside
     finally:
         for n in names:

@@ -45,7 +45,7 @@ with torch.no_grad():
     at = layer.self_attn
     print(f"  src + pos                {t(lambda: src + pos):8.2f} ms")
     print(f"  value_proj               {t(lambda: at.value_proj(src)):8.2f} ms")
-    w, b = at._fused_projection()
+    w, b = at._fused_projection()[:2]
     print(f"  offsets|logits proj      {t(lambda: F.linear(src.view(-1, C), w, b)):8.2f} ms")
     print(f"  self_attn (all)          {t(lambda: at(src, ref, src, ss, lsi, None, spatial_shapes_py=shapes_py)):8.2f} ms")
     print(f"  output_proj              {t(lambda: at.output_proj(src)):8.2f} ms")
