@@ -97,6 +97,10 @@ def get_default_cfg():
             "CL_PLUGIN": {"CL_PLUGIN_NAME": "CTCLPlugin", "REID_WEIGHT": 2.0, "AUX_REID_WEIGHT": 3.0, "NUM_NEGATIVES": 99,
                           "FUSION_LOSS": False, "BIO_CL": False, "ONE_DIRECTION": True, "MOMENTUM_EMBED": True,
                           "NOISE_EMBED": False},
+            # ov_dvis/config.py:16-22 (the open-vocabulary family: FCCLIPHead and the `_OV` transformer decoders)
+            "FC_CLIP": {"CLIP_MODEL_NAME": "convnext_large_d_320", "CLIP_PRETRAINED_WEIGHTS": "laion2b_s29b_b131k_ft_soup",
+                        "EMBED_DIM": 768, "GEOMETRIC_ENSEMBLE_ALPHA": 0.4, "GEOMETRIC_ENSEMBLE_BETA": 0.8,
+                        "ENSEMBLE_ON_VALID_MASK": False},
         },
         "INPUT": {"SAMPLING_FRAME_NUM": 1},
     })

@@ -359,3 +359,37 @@ def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale
     out = qkv.new_empty(B, H * W, C)
     out[:, src[valid]] = o[:, valid]
     return out
+
+
+# --- classification of the open-vocabulary (FC-CLIP) heads (csrc/mask_pool.hip, csrc/ov_class_logits.hip) ---------------------------
+def mask_pool(x, mask_logits):
+    """functions.mask_pool as torch ops: x (B, C, H, W), mask_logits (B, Q, H, W) (any strides) -> (sum (B, Q, C) of x over the pixels
+    with logit > 0 — false for 0.0, -0.0 and NaN —, count (B, Q) int32 of those pixels): MaskPooling
+    (ov_dvis/video_mask2former_transformer_decoder_ov.py:39-67) before its division."""
+    inside = mask_logits > 0
+    return torch.einsum("bchw,bqhw->bqc", x, inside.to(x.dtype)), inside.sum(dim=(-1, -2)).to(torch.int32)
+
+
+def text_class_logits(x, text_classifier, logit_scale, num_templates):
+    """get_classification_logits (ov_dvis/video_mask2former_transformer_decoder_ov.py:17-36) for x (..., D): normalise, scale by
+    min(exp(logit_scale), 100), multiply by text_classifier (N, D)^T and take the maximum over each group's templates ->
+    (..., len(num_templates)).  The groups are consecutive (the caller checked that they add up to N: the reference's "last n rows"
+    for the void group is then the same rows)."""
+    scale = torch.clamp(logit_scale.to(x.dtype).exp(), max=100)
+    logits = (scale * F.normalize(x, dim=-1)) @ text_classifier.to(x.dtype).T
+    return torch.stack([part.max(-1).values for part in logits.split([int(n) for n in num_templates], dim=-1)], dim=-1)
+
+
+def ov_ensemble(in_logits, out_logits, overlapping, alpha, beta, valid=None):
+    """The geometric ensemble of ov_dvis/meta_architecture_ov.py:603-642 on rows (..., K + 1), in the log domain (the contract of
+    dvis_ov_ensemble, include/dvis_hip.h): c_k = (1 - a_k) log_softmax(in[:K])_k + a_k log_softmax(out[:K])_k with a_k = alpha where
+    overlapping_k else beta, times (valid > 0) when given; -> log(cat(softmax(c) (1 - p_void), p_void) + 1e-8), p_void the softmax
+    of all K + 1 in-vocabulary logits at the last one."""
+    dt = in_logits.dtype
+    seen = overlapping.to(in_logits.device) != 0
+    a = torch.where(seen, torch.tensor(float(alpha), dtype=dt), torch.tensor(float(beta), dtype=dt))
+    if valid is not None:
+        a = a * (valid > 0).to(dt).unsqueeze(-1)
+    c = (1 - a) * torch.log_softmax(in_logits[..., :-1], -1) + a * torch.log_softmax(out_logits[..., :-1].to(dt), -1)
+    p_void = torch.softmax(in_logits, -1)[..., -1:]
+    return torch.log(torch.cat([torch.softmax(c, -1) * (1.0 - p_void), p_void], dim=-1) + 1e-8)

@@ -915,6 +915,155 @@ def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale
     return out
 
 
+# ---- classification of the open-vocabulary (FC-CLIP) heads: csrc/mask_pool.hip, csrc/ov_class_logits.hip ----------------------------
+MaskPoolPlan = collections.namedtuple("MaskPoolPlan", "slab slabs")
+
+
+def _no_backward(op, tensors):
+    """The open-vocabulary ops are inference-only on the GPU: an input that requires grad with grad enabled raises, naming the op."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError(f"{op}: there is no backward for {op} on the GPU (the open-vocabulary kernels are inference-only); call it "
+                           "under torch.no_grad() or detach its inputs")
+
+
+def mask_pool_plan(B, Q, C, H, W):
+    """How csrc/mask_pool.hip would pool x (B, C, H, W) under mask logits (B, Q, H, W), without launching it: MaskPoolPlan(slab,
+    slabs) — the pixels of one slab and the number of slabs whose partial sums are added in order, a function of H W alone.  Asked
+    of the library (dvis_mask_pool_plan, which applies the served-shape checks of the call itself: Q <= 256, C % 4 == 0 up to 2048,
+    frames below 2^31 bytes); a shape it does not serve raises, naming the value.  Only sizes are read: no GPU is needed."""
+    plan = (ctypes.c_int32 * 2)()
+    native.check(native.lib().dvis_mask_pool_plan(int(B), int(Q), int(C), int(H) * int(W), plan), "dvis_mask_pool_plan")
+    return MaskPoolPlan(plan[0], plan[1])
+
+
+def mask_pool(x, mask_logits):
+    """The sums and pixel counts of MaskPooling (ov_dvis/video_mask2former_transformer_decoder_ov.py:39-67): x (B, C, H, W) and
+    mask_logits (B, Q, H, W) -> (sum (B, Q, C) of x over the pixels with logit > 0, count (B, Q) int32 of those pixels).  0.0, -0.0
+    and NaN logits are outside the mask.  The mean is ``mask_pool_mean``; sums and counts come separately because the refiner
+    combines frames by their pixel counts.
+    GPU: csrc/mask_pool.hip (contract: dvis_mask_pool in include/dvis_hip.h) on float32 tensors, x contiguous; mask_logits may be any
+    view whose (H, W) planes are contiguous — a frame ``logits[0, :, t]`` of the (1, Q, T, H, W) inference logits is read in place.
+    Exact fp32, no atomics: the same bits on every call, and a frame's bits do not depend on B.  A shape outside the served domain
+    (``mask_pool_plan``) raises.  CPU tensors (any float dtype) take cpu_ops.mask_pool.  No backward on the GPU."""
+    if x.dim() != 4 or mask_logits.dim() != 4 or x.shape[0] != mask_logits.shape[0] or x.shape[-2:] != mask_logits.shape[-2:]:
+        raise RuntimeError(f"mask_pool: expected x (B, C, H, W) and mask_logits (B, Q, H, W) on one map size; got {tuple(x.shape)} and "
+                           f"{tuple(mask_logits.shape)} (MaskPooling interpolates differing sizes before it pools)")
+    if _on_cpu(x, mask_logits):
+        return cpu_ops.mask_pool(x, mask_logits)
+    _no_backward("mask_pool", (x, mask_logits))
+    B, C, H, W = x.shape
+    Q = mask_logits.shape[1]
+    px = _f32_gpu(x, "x")
+    if not (mask_logits.is_cuda and mask_logits.device == x.device and mask_logits.dtype == torch.float32):
+        raise RuntimeError(f"mask_pool: mask_logits must be a float32 tensor on x's GPU (got {mask_logits.dtype} on {mask_logits.device})")
+    if H * W > 1 and not ((W == 1 or mask_logits.stride(3) == 1) and (H == 1 or mask_logits.stride(2) == W)):
+        raise RuntimeError(f"mask_pool: the (H, W) planes of mask_logits must be contiguous (got strides {mask_logits.stride()})")
+    dev = x.device
+    total = torch.empty((B, Q, C), dtype=torch.float32, device=dev)
+    count = torch.empty((B, Q), dtype=torch.int32, device=dev)
+    lib = native.lib()
+    nbytes = lib.dvis_mask_pool_ws_bytes(B, Q, C, H * W)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        rc = lib.dvis_mask_pool(px, ctypes.c_void_p(mask_logits.data_ptr()), mask_logits.stride(0) if B > 1 else 0,
+                                mask_logits.stride(1) if Q > 1 else H * W, B, Q, C, H * W, native.dev_ptr(total, "sum"),
+                                native.dev_ptr(count, "count"), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                native.stream_ptr(dev))
+    native.check(rc, "dvis_mask_pool")
+    return total, count
+
+
+def mask_pool_mean(x, mask_logits):
+    """MaskPooling.forward(x, mask, return_num=True): (pooled (B, Q, C) = sum / (count + 1e-8), denorm (B, Q, 1, 1) = count + 1e-8),
+    computed as the reference does — a row without a pixel pools to exactly 0."""
+    total, count = mask_pool(x, mask_logits)
+    denorm = count.to(total.dtype) + 1e-8
+    return total / denorm.unsqueeze(-1), denorm[..., None, None]
+
+
+_seg_ptr_cache = {}
+
+
+def _seg_ptr(num_templates, N, device):
+    """Device int32 prefix sums of num_templates (K + 2 entries), cached per (device, tuple).  An inconsistent list raises."""
+    key = tuple(int(n) for n in num_templates)
+    if not key or min(key) < 1 or sum(key) != N:
+        raise RuntimeError(f"text_class_logits: num_templates must list at least one template per group (the void group last) and add "
+                           f"up to the {N} rows of text_classifier; got {len(key)} groups adding up to {sum(key)}"
+                           + (f", smallest {min(key)}" if key else ""))
+    hit = _seg_ptr_cache.get((str(device), key))
+    if hit is None:
+        hit = _seg_ptr_cache[(str(device), key)] = torch.tensor([0, *key], dtype=torch.int64).cumsum(0).to(torch.int32).to(device)
+    return hit
+
+
+def text_class_logits(x, text_classifier, logit_scale, num_templates):
+    """get_classification_logits (ov_dvis/video_mask2former_transformer_decoder_ov.py:17-36): x (..., D), text_classifier (N, D),
+    logit_scale a 0-d tensor (a parameter: read on the device, no synchronisation), num_templates the templates per class with the
+    void group last -> (..., K + 1) = max over a group's templates of min(exp(logit_scale), 100) * normalize(x) @ text^T.
+    num_templates must add up to N with no empty group (the reference silently takes "the last n rows" for the void group; with a
+    consistent list the two agree).
+    GPU, float32: the products on the exact-fp32 GEMM (gemm_nt on the raw x; D % 4 == 0), then ONE epilogue launch for the row
+    norm, the scale and the segmented maximum (csrc/ov_class_logits.hip).  CPU tensors (any float dtype): cpu_ops.  No backward on
+    the GPU."""
+    N, D = text_classifier.shape
+    if x.shape[-1] != D or not torch.is_tensor(logit_scale) or logit_scale.numel() != 1:
+        raise RuntimeError(f"text_class_logits: expected x (..., D), text_classifier (N, D) and a one-element logit_scale tensor; got "
+                           f"{tuple(x.shape)}, {tuple(text_classifier.shape)}")
+    seg = _seg_ptr(num_templates, N, x.device)
+    if _on_cpu(x, text_classifier, logit_scale):
+        return cpu_ops.text_class_logits(x, text_classifier, logit_scale, num_templates)
+    _no_backward("text_class_logits", (x, text_classifier, logit_scale))
+    for name, t in (("x", x), ("text_classifier", text_classifier), ("logit_scale", logit_scale)):
+        if not (t.is_cuda and t.device == x.device and t.dtype == torch.float32):
+            raise RuntimeError(f"text_class_logits: {name} must be a float32 tensor on x's GPU (got {t.dtype} on {t.device})")
+    x2, ldx = _rows2d(x.detach(), D)
+    dots = gemm_nt(x2, text_classifier.detach())                                                # (R, N)
+    R, K1 = x2.shape[0], seg.numel() - 1
+    out = torch.empty((*x.shape[:-1], K1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = native.lib().dvis_text_class_logits(ctypes.c_void_p(x2.data_ptr()), ldx, native.dev_ptr(dots, "dots"), N,
+                                                 ctypes.c_void_p(logit_scale.data_ptr()), native.dev_ptr(seg, "seg_ptr"), R, D, N, K1,
+                                                 native.dev_ptr(out, "out"), native.stream_ptr(x.device))
+    native.check(rc, "dvis_text_class_logits")
+    return out
+
+
+def ov_ensemble(in_logits, out_logits, overlapping, alpha, beta, valid=None):
+    """The geometric ensemble of the open-vocabulary meta-architectures (ov_dvis/meta_architecture_ov.py:603-642) in one launch
+    (contract: dvis_ov_ensemble in include/dvis_hip.h): in_logits / out_logits (..., K + 1) in- / out-vocabulary class logits with
+    void last, overlapping (K) non-zero where the category was seen in training (alpha there, beta elsewhere), valid (...) integer
+    pixel counts or None (ENSEMBLE_ON_VALID_MASK: rows with valid <= 0 keep the in-vocabulary distribution) ->
+    log(cat(softmax(c) (1 - p_void), p_void) + 1e-8), evaluated in the log domain.  GPU: float32, K <= 2048.  CPU tensors (any float
+    dtype): cpu_ops.ov_ensemble.  No backward on the GPU."""
+    K = in_logits.shape[-1] - 1
+    if in_logits.shape != out_logits.shape or K < 1 or overlapping.numel() != K \
+            or (valid is not None and tuple(valid.shape) != tuple(in_logits.shape[:-1])):
+        raise RuntimeError(f"ov_ensemble: expected in_logits and out_logits (..., K + 1), overlapping (K) and valid (...); got "
+                           f"{tuple(in_logits.shape)}, {tuple(out_logits.shape)}, {tuple(overlapping.shape)}"
+                           + ("" if valid is None else f", {tuple(valid.shape)}"))
+    if _on_cpu(in_logits, out_logits):
+        return cpu_ops.ov_ensemble(in_logits, out_logits, overlapping.reshape(K), alpha, beta, valid)
+    _no_backward("ov_ensemble", (in_logits, out_logits))
+    dev = in_logits.device
+    for name, t in (("in_logits", in_logits), ("out_logits", out_logits)):
+        if not (t.is_cuda and t.device == dev and t.dtype == torch.float32):
+            raise RuntimeError(f"ov_ensemble: {name} must be a float32 tensor on in_logits' GPU (got {t.dtype} on {t.device})")
+    a, b = in_logits.contiguous(), out_logits.contiguous()
+    ov = overlapping.reshape(K).to(device=dev, dtype=torch.float32).contiguous()
+    vp = None
+    if valid is not None:
+        valid = valid.to(device=dev, dtype=torch.int32).contiguous()
+        vp = native.dev_ptr(valid, "valid")
+    out = torch.empty_like(a)
+    with torch.cuda.device(dev):
+        rc = native.lib().dvis_ov_ensemble(native.dev_ptr(a, "in_logits"), native.dev_ptr(b, "out_logits"), native.dev_ptr(ov, "overlapping"),
+                                           vp, float(alpha), float(beta), a.numel() // (K + 1), K, native.dev_ptr(out, "out"),
+                                           native.stream_ptr(dev))
+    native.check(rc, "dvis_ov_ensemble")
+    return out
+
+
 def vps_argmax(mask_logits_kthw, scores, first_resize_size, img_size, out_hw):
     """Fused panoptic arg-max (see dvis_vps_argmax).  mask_logits_kthw: float32 GPU (K, T, h, w) view whose last two
     dims are contiguous; scores float32 (K,).  Returns ids int32 (T,H,W), conf bool (T,H,W), areas int32 (3, K)."""

@@ -83,6 +83,35 @@ class MaskFormerHead(nn.Module):
         return self.predictor(multi_scale_features, mask_features, mask)
 
 
+@SEM_SEG_HEADS_REGISTRY.register()
+class FCCLIPHead(MaskFormerHead):
+    """mask2former/modeling/meta_arch/mask_former_head.py:155-231: the head of the open-vocabulary family.  As MaskFormerHead, and
+    the text classifier travels in the feature dict: ``features["text_classifier"]`` (N, clip_embedding_dim) and
+    ``features["num_templates"]`` are passed through to the predictor (an `_OV` transformer decoder)."""
+
+    @configurable
+    def __init__(self, input_shape=None, *, num_classes, pixel_decoder, loss_weight=1.0, ignore_value=-1, transformer_predictor,
+                 transformer_in_feature):
+        super().__init__(input_shape, num_classes=num_classes, pixel_decoder=pixel_decoder, loss_weight=loss_weight,
+                         ignore_value=ignore_value, transformer_predictor=transformer_predictor,
+                         transformer_in_feature=transformer_in_feature)
+
+    @classmethod
+    def from_config(cls, cfg, input_shape):
+        ret = MaskFormerHead.from_config.__func__(cls, cfg, input_shape)
+        del ret["return_transformer_feature"]
+        return ret
+
+    @Fn.fp32_island
+    def forward(self, features, mask=None):
+        mask_features, _, multi_scale_features = self.pixel_decoder.forward_features(features)
+        return self.predictor(multi_scale_features, mask_features, mask, text_classifier=features["text_classifier"],
+                              num_templates=features["num_templates"])
+
+    def layers(self, features, mask=None):
+        return self.forward(features, mask)
+
+
 def segmenter_frames_per_call(n, H, W, requested=0):
     """Frames per segmenter call for n frames (requested: the user's chunk, 0 = all of them in one call), cut into equal
     shares.  (Rounds 1-2 capped a call at 4 GiB per activation — 55 frames at 720p — because two segmenter passes in

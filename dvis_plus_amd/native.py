@@ -166,6 +166,11 @@ SIGNATURES = {
                                              _p, _p, _p]),
     "dvis_window_attention_supported": (_i, [_i, _i]),
     "dvis_window_attention": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
+    "dvis_mask_pool_plan": (_i, [_i, _i, _i, _i64, _p]),
+    "dvis_mask_pool_ws_bytes": (_i64, [_i, _i, _i, _i64]),
+    "dvis_mask_pool": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _i64, _p, _p, _p, _p]),
+    "dvis_text_class_logits": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "dvis_ov_ensemble": (_i, [_p, _p, _p, _p, _f, _f, _i, _i, _p, _p]),
 }
 
 _lib = None

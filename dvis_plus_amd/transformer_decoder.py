@@ -7,6 +7,9 @@ Mirrors (constructor arguments, attribute names, ``state_dict`` keys):
   VideoMultiScaleMaskedTransformerDecoder_minvis/_dvis ibid. :11-171 (same layers, no re-id head)
   MultiScaleMaskedTransformerDecoder (image, BASELINE config #1)
         mask2former/modeling/transformer_decoder/mask2former_transformer_decoder.py:207-461
+  MaskPooling / get_classification_logits / VideoMultiScaleMaskedTransformerDecoder_dvis_OV / _minvis_OV (open vocabulary: the
+        FC-CLIP class head on Fn.mask_pool and Fn.text_class_logits; inference only)
+        ov_dvis/video_mask2former_transformer_decoder_ov.py:17-377
 
 Inference-only re-organisation for MI355X (same numbers as the reference's eval path):
   * frames are the batch; the K / V projections of ALL layers that read a feature level are ONE GEMM per level
@@ -23,6 +26,8 @@ Under ``.train()`` all four classes run ``_train_layers`` instead: the reference
 (cross-attention; backward csrc/masked_attention_backward.hip), ``Fn.attention`` (self-attention) and ``Fn.mask_logits``.
 The training maths of a layer is its class's ``train_forward`` — the one spelling the decoders, the tracker and the refiner call.
 """
+import math
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -554,5 +559,123 @@ class VideoMultiScaleMaskedTransformerDecoder_minvis(VideoMultiScaleMaskedTransf
 
     def forward(self, x, mask_features, mask=None):
         out = super().forward(x, mask_features, mask=mask)
+        del out["mask_features"]
+        return out
+
+
+# ---- open-vocabulary (FC-CLIP) heads: ov_dvis/video_mask2former_transformer_decoder_ov.py ---------------------------------------------
+
+def get_classification_logits(x, text_classifier, logit_scale, num_templates=None):
+    """…decoder_ov.py:17-36: x (B, *, C), text_classifier (N, C), logit_scale a scalar parameter, num_templates the templates per
+    class with the void group last -> (B, *, K + 1).  One GEMM and one epilogue launch (Fn.text_class_logits)."""
+    return Fn.text_class_logits(x, text_classifier, logit_scale, num_templates)
+
+
+class MaskPooling(nn.Module):
+    """…decoder_ov.py:39-67: the mean of x (B, C, H, W) under every query's own mask (`logit > 0`) -> (B, Q, C); return_num also
+    returns the denominators (B, Q, 1, 1) = pixel count + 1e-8.  Masks of another size are resized first, with torch as in the
+    reference.  The binary mask tensor is never written (Fn.mask_pool)."""
+
+    def forward(self, x, mask, return_num=False):
+        if not x.shape[-2:] == mask.shape[-2:]:
+            mask = F.interpolate(mask, size=x.shape[-2:], mode="bilinear", align_corners=False)
+        pooled, denorm = Fn.mask_pool_mean(x, mask.detach())
+        return (pooled, denorm) if return_num else pooled
+
+
+@TRANSFORMER_DECODER_REGISTRY.register()
+class VideoMultiScaleMaskedTransformerDecoder_dvis_OV(_MaskedDecoderBase):
+    """The per-frame decoder of the open-vocabulary family (…decoder_ov.py:69-366): the layers of `_dvis`, and a class head that
+    has no Linear(hidden, K + 1) — a query is classified by the mean of mask_features under its own mask, projected, added to the
+    normalised query, taken to CLIP space by a 3-layer MLP and compared with the text classifier's rows.
+
+    Inference only.  Eval returns the last prediction (`aux_outputs` is [], as for the other decoders); under ``.train()`` within
+    ``torch.no_grad()`` — how the open-vocabulary tracker and refiner stages run the frozen segmenter — all L + 1 predictions come
+    back, the (b t) frames split by num_frames, computed by the SAME layer and head calls as in eval: the last one equals eval's bit
+    for bit.  With grad enabled and a trainable parameter the forward raises: mask pooling and the text logits have no backward."""
+
+    @configurable
+    def __init__(self, in_channels, mask_classification=True, *, num_classes, hidden_dim, num_queries, nheads,
+                 dim_feedforward, dec_layers, pre_norm, mask_dim, enforce_input_project, clip_embedding_dim, num_frames):
+        super().__init__(in_channels, mask_classification, num_classes=num_classes, hidden_dim=hidden_dim,
+                         num_queries=num_queries, nheads=nheads, dim_feedforward=dim_feedforward,
+                         dec_layers=dec_layers, pre_norm=pre_norm, mask_dim=mask_dim,
+                         enforce_input_project=enforce_input_project)
+        self.num_frames = num_frames
+        self.mask_pooling = MaskPooling()
+        self._mask_pooling_proj = nn.Sequential(nn.LayerNorm(hidden_dim), nn.Linear(hidden_dim, hidden_dim))
+        self.class_embed = MLP(hidden_dim, hidden_dim, clip_embedding_dim, 3)      # (replaces the closed-vocabulary Linear)
+        self.logit_scale = nn.Parameter(torch.ones([]) * math.log(1 / 0.07))
+        self.debug_pooled = None     # tests: a list here receives every prediction's (pooled embeddings (N, Q, C), counts (N, Q))
+
+    @classmethod
+    def from_config(cls, cfg, in_channels, mask_classification):
+        ret = cls._base_from_config(cfg, in_channels, mask_classification)
+        ret.update(num_frames=cfg.INPUT.SAMPLING_FRAME_NUM, clip_embedding_dim=cfg.MODEL.FC_CLIP.EMBED_DIM)
+        return ret
+
+    def forward_prediction_heads(self, output, mask_features, text_classifier, num_templates):
+        """…decoder_ov.py:331-353 without the attention mask (the layers make their own): output (Q, N, C) un-normed ->
+        (class logits (N, Q, K + 1), mask logits (N, Q, H, W), decoder_norm(output) as (N, Q, C)).  Mask pooling reads the mask
+        logits that were written anyway."""
+        dec = self.decoder_norm(output).transpose(0, 1)                                         # (N, Q, C)
+        masks = Fn.mask_logits(self.mask_embed(dec).contiguous(), mask_features)
+        total, count = Fn.mask_pool(mask_features, masks)
+        pooled = total / (count.to(total.dtype) + 1e-8).unsqueeze(-1)                           # MaskPooling's mean
+        if self.debug_pooled is not None:
+            self.debug_pooled.append((pooled, count))
+        norm, proj = self._mask_pooling_proj
+        emb = self.class_embed(Fn.linear(norm(pooled), proj.weight, proj.bias) + dec)
+        return get_classification_logits(emb, text_classifier, self.logit_scale, num_templates), masks, dec
+
+    @Fn.fp32_island
+    def forward(self, x, mask_features, mask=None, text_classifier=None, num_templates=None, clip_size=1):
+        """Shapes as in the reference: pred_logits (b, t, Q, K + 1), pred_masks (b, Q, t, H, W), pred_embds /
+        pred_embds_without_norm (b, C, t, Q), mask_features ((b t), Cm, H, W); b = 1 in eval."""
+        assert len(x) == self.num_feature_levels
+        if text_classifier is None or num_templates is None:
+            raise ValueError(f"{type(self).__name__}: text_classifier (N, {self.class_embed.layers[-1].out_features}) and "
+                             "num_templates are required — an open-vocabulary decoder has no class weights of its own")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise NotImplementedError(
+                f"{type(self).__name__}: training the open-vocabulary heads is not implemented — mask_pool and text_class_logits have no "
+                "backward.  Run the frozen segmenter under torch.no_grad() (in .train() it returns all L + 1 predictions) or freeze its "
+                "parameters")
+        del mask                                                                                # (the reference disables it too)
+        x, mask_features = self._f32_inputs(x, mask_features)
+        mask_features = mask_features.contiguous()
+        N = x[0].shape[0]
+        heads = lambda o: self.forward_prediction_heads(o, mask_features, text_classifier, num_templates)
+        if not self.training:
+            b, t = 1, N
+            output = self._run_layers(x, mask_features)
+            preds = [heads(output)]
+        else:
+            # every layer's residual stream, from the layers of _run_layers themselves: a forward hook on each FFN (a layer's last op)
+            b, t = self._train_clips(N)
+            streams = [self.query_feat.weight.unsqueeze(1).repeat(1, N, 1)]
+            hooks = [ffn.register_forward_hook(lambda m, args, out: streams.append(out)) for ffn in self.transformer_ffn_layers]
+            try:
+                output = self._run_layers(x, mask_features)
+            finally:
+                for h in hooks:
+                    h.remove()
+            assert len(streams) == self.num_layers + 1 and streams[-1] is output
+            preds = [heads(o) for o in streams]
+        out = self._train_video_outputs(b, t, [p[0] for p in preds], [p[1] for p in preds])
+        if not self.training:
+            out["aux_outputs"] = []
+        out.update(pred_embds=self._train_bctq(preds[-1][2], b, t),
+                   pred_embds_without_norm=self._train_bctq(output.transpose(0, 1), b, t), mask_features=mask_features)
+        return out
+
+
+@TRANSFORMER_DECODER_REGISTRY.register()
+class VideoMultiScaleMaskedTransformerDecoder_minvis_OV(VideoMultiScaleMaskedTransformerDecoder_dvis_OV):
+    """MinVIS open-vocabulary: the `_dvis_OV` decoder without `mask_features` in its outputs (…decoder_ov.py:368-377)."""
+
+    def forward(self, x, mask_features, mask=None, text_classifier=None, num_templates=None, clip_size=1):
+        out = super().forward(x, mask_features, mask=mask, text_classifier=text_classifier, num_templates=num_templates,
+                              clip_size=clip_size)
         del out["mask_features"]
         return out

@@ -986,6 +986,54 @@ int dvis_window_attention_supported(int ws, int d);
 int dvis_window_attention(const float *qkv, const float *qkv_bias, const float *bias_table, float *out, int B, int H, int W, int heads,
                           int d, int ws, int shift, float scale, void *stream);
 
+/*
+ * Mask pooling of the open-vocabulary (FC-CLIP) heads (csrc/mask_pool.hip; MaskPooling,
+ * ov_dvis/video_mask2former_transformer_decoder_ov.py:39-67, without its mean):
+ *   sum[b, q, c] = sum over the pixels p with logits[b, q, p] > 0 of x[b, c, p]      count[b, q] = the number of those pixels
+ *   x (B, C, HW) contiguous; logits: (HW) planes, contiguous each, at logits + b * l_bstride + q * l_qstride (strides in ELEMENTS,
+ *   l_qstride >= HW: a frame of the (1, Q, T, H, W) inference logits is pooled in place); sum (B, Q, C) fp32; count (B, Q) int32.
+ * Membership is a select on the loaded logit: 0.0, -0.0 and NaN are outside, every positive value (denormals included) inside.  The
+ * selected 0 / 1 operand and x go through the exact-fp32 MFMA (a k-ordered fma chain): a non-finite x of a frame reaches every row
+ * of that frame, as through the reference's einsum, and no other frame.  The mean, its `+ 1e-8` and any combination over frames
+ * are the caller's.
+ * Served: 1 <= Q <= 256, C % 4 == 0 up to 2048 (chunks of 128 channels), any HW >= 1 (rows need not be 16-byte aligned), one
+ * frame of x and of the logits below 2^31 bytes, 16 consecutive query planes spanning less than 2^31 bytes; anything else is
+ * refused before the launch, naming the value.
+ * The pixels are cut into ceil(HW / 512) slabs — a function of HW alone (dvis_mask_pool_plan: the served-shape checks of the call
+ * itself, then plan[0] = the slab size, plan[1] = the slab count; no GPU needed) —, partials go to `ws` and are added in slab order: no float atomics, the same bits on every call, a frame's
+ * bits do not depend on B; every element of sum and count is written.  No memset, no host synchronisation: capturable.
+ * ws: dvis_mask_pool_ws_bytes bytes (0, and ws may be null, when there is one slab).
+ */
+int dvis_mask_pool_plan(int B, int Q, int C, int64_t HW, int32_t *plan);
+int64_t dvis_mask_pool_ws_bytes(int B, int Q, int C, int64_t HW);
+int dvis_mask_pool(const float *x, const float *logits, int64_t l_bstride, int64_t l_qstride, int B, int Q, int C, int64_t HW,
+                   float *sum, int32_t *count, void *ws, void *stream);
+
+/*
+ * Epilogue of get_classification_logits (ov_dvis/video_mask2former_transformer_decoder_ov.py:17-36) on the products of the exact
+ * GEMM (csrc/ov_class_logits.hip):
+ *   out[r, k] = max over n in [seg_ptr[k], seg_ptr[k + 1]) of  s * dots[r, n] / max(||x_r||, 1e-12),  s = min(exp(*logit_scale), 100)
+ *   x (R, D) and dots (R, N) = x text^T with row strides in elements; logit_scale: ONE DEVICE float; seg_ptr (K1 + 1) int32 DEVICE
+ *   prefix sums of num_templates over the K1 = K + 1 groups (the void group last), seg_ptr[0] = 0, seg_ptr[K1] = N, no empty
+ *   group (the caller checks the list); out (R, K1).  One launch, fixed-order norm: the same bits on every call.
+ */
+int dvis_text_class_logits(const float *x, int64_t x_stride, const float *dots, int64_t dots_stride, const float *logit_scale,
+                           const int32_t *seg_ptr, int R, int D, int N, int K1, float *out, void *stream);
+
+/*
+ * Geometric ensemble of the open-vocabulary meta-architectures (ov_dvis/meta_architecture_ov.py:603-642), one launch:
+ *   in_logits, out_logits, out (R, K + 1) contiguous; overlapping (K) fp32, non-zero = seen category; valid (R) int32 or null
+ *   (ENSEMBLE_ON_VALID_MASK: a row with valid <= 0 takes a = 0).
+ *   p_in, p_out = softmax of the first K logits; a_k = (overlapping_k ? alpha : beta) * (valid_r > 0);
+ *   c_k = log(p_in_k^(1 - a_k) p_out_k^(a_k)); p_void = softmax(in_logits[r, :K + 1])[K];
+ *   out[r] = log(cat(softmax(c) * (1 - p_void), p_void) + 1e-8).
+ * The geometric mean is evaluated in the log domain (c_k = (1 - a_k) log p_in_k + a_k log p_out_k from log-sum-exps): the
+ * reference's fp32 `p ** a` underflows to log 0 at CLIP's logit scale; after the final `+ 1e-8` both forms agree wherever the
+ * reference's is finite.  Served: 1 <= K <= 2048.
+ */
+int dvis_ov_ensemble(const float *in_logits, const float *out_logits, const float *overlapping, const int32_t *valid, float alpha,
+                     float beta, int R, int K, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
