@@ -444,10 +444,198 @@ __global__ __launch_bounds__(256) void upsample_add_image_kernel(const float *__
   }
 }
 
+// The same image, second form (W % 4 == 0): the bytes travel differently, every value is computed by the operations above.
+//   * one workgroup = (64-channel chunk, 32-pixel group, kUpRows output rows of one frame);
+//   * the top taps of the whole block are staged ONCE in LDS ([top row][channel][top x], at most kUpTR x kUpTX taps per channel:
+//     a 2x block needs 6 x 18): every tap is fetched once per block instead of once per output pixel and row that uses it.
+//     TOK: `top` is token-major — (N, S, C) rows starting at row0, one token = C contiguous floats (a level of the encoder
+//     memory where it lies) — and is staged with 16-byte loads of four channels; otherwise (N, C, h, w);
+//   * the lateral is read with one 16-byte load per lane: four consecutive pixels of one channel, the next row's in flight;
+//   * the sums are transposed through LDS (a pixel's 64 channels in a row of 68 floats: the 16-byte slot of pixel x is
+//     x + const mod 16, distinct over every lane group of ds_read_b128) into the fragment order and leave through store_fragments2.
+// Operation order: what hipcc makes of the expression in upsample_add_image_kernel, written out (contraction off here).  Of the
+// eight channels of a fragment, the LAST one (e = 7: chunk channels with (c & 11) == 11) went through the packed-math unit there:
+// its upper row's horizontal term is fma(lx1, t01, lx0 * t00) instead of fma(lx0, t00, lx1 * t01), and its two rows are added
+// after rounding both products.  tests/test_upsample_add_image_v2_gpu.py holds the two forms to equal bytes.
+constexpr int kUpRows = 8, kUpTR = 6, kUpTX = 18, kUpTXS = 19, kUpPix = 68;
+
+template <bool TOK>
+__global__ __launch_bounds__(256) void upsample_add_image_v2_kernel(const float *__restrict__ lateral, const float *__restrict__ top,
+                                                                    void *__restrict__ img, int N, int C, int H, int W, int h, int w,
+                                                                    const float *__restrict__ lat_scale,
+                                                                    const float *__restrict__ lat_shift, float oscale, int HB,
+                                                                    long long tokS, long long row0) {
+#pragma clang fp contract(off)
+  __shared__ float topt[kUpTR * 64 * kUpTXS];
+  __shared__ __attribute__((aligned(16))) float tr[32 * kUpPix];
+  const int NCC = C / 64, XG = (W + 31) / 32;
+  const int cc = blockIdx.x, xg = blockIdx.y;
+  const int n = (int)blockIdx.z / HB, yb = ((int)blockIdx.z - n * HB) * kUpRows;
+  const int t = threadIdx.x;
+  const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+  auto src_x = [&](int px, int &x0, int &x1, float &l1) {      // px < W
+    float fx = __builtin_fmaf(sx, (float)px + 0.5f, -0.5f);
+    fx = fx < 0.f ? 0.f : fx;
+    x0 = min((int)fx, w - 1), x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    l1 = fx - (float)x0;
+  };
+  auto src_y = [&](int y, int &y0, int &y1, float &l1) {
+    float fy = __builtin_fmaf(sy, (float)y + 0.5f, -0.5f);
+    fy = fy < 0.f ? 0.f : fy;
+    y0 = min((int)fy, h - 1), y1 = y0 + (y0 < h - 1 ? 1 : 0);
+    l1 = fy - (float)y0;
+  };
+  // the block's taps: top rows [ty0, ty1], top columns [tx0, tx1] (the host has checked that they fit)
+  const int ylast = min(yb + kUpRows, H) - 1;
+  int ty0, ty1, tx0, tx1, unused;
+  float unusedf;
+  src_y(yb, ty0, unused, unusedf);
+  src_y(ylast, unused, ty1, unusedf);
+  src_x(min(32 * xg, W - 1), tx0, unused, unusedf);
+  src_x(min(32 * xg + 31, W - 1), unused, tx1, unusedf);
+  const int nty = min(ty1 - ty0 + 1, kUpTR), ntx = min(tx1 - tx0 + 1, kUpTX);
+  if constexpr (TOK) {
+    const float *tb = top + ((size_t)n * (size_t)tokS + (size_t)row0) * (size_t)C + 64 * cc;
+    for (int i = t; i < nty * ntx * 16; i += 256) {
+      const int c4 = i & 15, p = i >> 4, r = p / ntx, xx = p - r * ntx;
+      const f4 v = *(const f4 *)(tb + ((size_t)(ty0 + r) * w + (tx0 + xx)) * (size_t)C + 4 * c4);
+      float *d = topt + (r * 64 + 4 * c4) * kUpTXS + xx;
+      d[0] = v.x, d[kUpTXS] = v.y, d[2 * kUpTXS] = v.z, d[3 * kUpTXS] = v.w;
+    }
+  } else {
+    for (int i = t; i < nty * 64 * 32; i += 256) {
+      const int xx = i & 31, c = (i >> 5) & 63, r = i >> 11;
+      if (xx < ntx) topt[(r * 64 + c) * kUpTXS + xx] = top[(((size_t)n * C + 64 * cc + c) * h + ty0 + r) * (size_t)w + tx0 + xx];
+    }
+  }
+  // the producer side: lane (channel ca + 32 i, quad q) makes pixels 4 q .. 4 q + 3 of its two channels
+  const int q = t & 7, ca = t >> 3;
+  const bool packed = (ca & 11) == 11;
+  const int qx = 32 * xg + 4 * q;
+  const bool inside = qx < W;                  // (a quad past the row's end repeats the row's last pixel, as the first form does)
+  const int qxc = inside ? qx : W - 4;
+  int xr0[4], xr1[4];
+  float lx0[4], lx1[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int x0, x1;
+    src_x(inside ? qx + j : W - 1, x0, x1, lx1[j]);
+    lx0[j] = 1.f - lx1[j];
+    xr0[j] = min(max(x0 - tx0, 0), kUpTX - 1), xr1[j] = min(max(x1 - tx0, 0), kUpTX - 1);
+  }
+  float sc[2] = {1.f, 1.f}, sh[2] = {0.f, 0.f};
+  const float *lp[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const size_t pl = (size_t)n * C + 64 * cc + ca + 32 * i;
+    if (lat_scale) sc[i] = lat_scale[pl], sh[i] = lat_shift[pl];
+    lp[i] = lateral + pl * (size_t)H * (size_t)W + qxc;
+  }
+  const __amdgpu_buffer_rsrc_t ri = dvis_make_rsrc_uniform(img, (unsigned)((long long)N * H * XG * NCC * 8192));
+  // the consumer side: thread (k-step S, half g, pixel x) splits the 8 channels of its fragment
+  const int x = t & 31, g = (t >> 5) & 1, S = t >> 6;
+  f4 lat[2], nlat[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) nlat[i] = *(const f4 *)(lp[i] + (size_t)yb * W);
+  __syncthreads();
+  for (int y = yb; y <= ylast; ++y) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) lat[i] = nlat[i];
+    if (y < ylast) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) nlat[i] = *(const f4 *)(lp[i] + (size_t)(y + 1) * W);
+    }
+    int y0, y1;
+    float ly1;
+    src_y(y, y0, y1, ly1);
+    const float ly0 = 1.f - ly1;
+    const int r0 = min(max(y0 - ty0, 0), kUpTR - 1), r1 = min(max(y1 - ty0, 0), kUpTR - 1);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const float *t0 = topt + (r0 * 64 + ca + 32 * i) * kUpTXS, *t1 = topt + (r1 * 64 + ca + 32 * i) * kUpTXS;
+      const float lv[4] = {lat[i].x, lat[i].y, lat[i].z, lat[i].w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float l = inside ? lv[j] : lv[3];
+        if (lat_scale) l = __builtin_fmaf(l, sc[i], sh[i]);
+        const float t00 = t0[xr0[j]], t01 = t0[xr1[j]], t10 = t1[xr0[j]], t11 = t1[xr1[j]];
+        const float h1 = __builtin_fmaf(lx0[j], t10, lx1[j] * t11);
+        const float h0 = packed ? __builtin_fmaf(lx1[j], t01, lx0[j] * t00) : __builtin_fmaf(lx0[j], t00, lx1[j] * t01);
+        const float v = packed ? ly0 * h0 + ly1 * h1 : __builtin_fmaf(ly0, h0, ly1 * h1);
+        tr[(4 * q + j) * kUpPix + ca + 32 * i] = l + v;
+      }
+    }
+    __syncthreads();
+    const f4 p0 = *(const f4 *)(tr + x * kUpPix + 16 * S + 4 * g), p1 = *(const f4 *)(tr + x * kUpPix + 16 * S + 4 * g + 8);
+    h8 hi, lo;
+    split8(p0, p1, oscale, hi, lo);
+    const unsigned G = ((unsigned)n * (unsigned)H + (unsigned)y) * (unsigned)XG + (unsigned)xg;
+    const unsigned off = (G * (unsigned)NCC + (unsigned)cc) * 8192u + (unsigned)(S * 2048 + g * 512 + x * 16);
+    store_fragments2(ri, off, hi, 0, lo, 1024);
+    __syncthreads();
+  }
+}
+
 }  // namespace
 
 /* image (C channels, dvis_conv_x3_image_bytes(N, C, H, W)) = split(lateral * scale + shift + bilinear(top)): dvis_upsample_add[_affine]
  * with the result as an operand image for an image-input convolution; lat_scale / lat_shift per plane or NULL */
+// The second form (upsample_add_image_v2_kernel) is on unless DVIS_UPSAMPLE_IMAGE_V2=0; dvis_upsample_add_image_set_v2 switches it
+// (the tests compare the two forms in one process) and returns the previous setting; on < 0 only reads it.
+static int g_upsample_v2 = [] {
+  const char *e = getenv("DVIS_UPSAMPLE_IMAGE_V2");
+  return e && e[0] == '0' && e[1] == 0 ? 0 : 1;
+}();
+
+DVIS_EXPORT int dvis_upsample_add_image_set_v2(int on) {
+  if (on < 0) return __atomic_load_n(&g_upsample_v2, __ATOMIC_RELAXED);
+  return __atomic_exchange_n(&g_upsample_v2, on ? 1 : 0, __ATOMIC_RELAXED);
+}
+
+/* Does the second form serve the shape?  W % 4 == 0 (16-byte lateral loads) and a block's taps — the top rows under kUpRows output
+ * rows, the top columns under 32 output pixels, one more on either side — within the staged tile (any up-sampling by 2 or more;
+ * 1e-3: the kernel's float coordinates may differ from these by rounding). */
+DVIS_EXPORT int dvis_upsample_add_image_v2_supported(int N, int C, int H, int W, int h, int w) {
+  if (N <= 0 || C <= 0 || C % 64 != 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || W % 4 != 0) return 0;
+  const int ry = (int)((kUpRows - 1) * (double)h / H + 1e-3) + 3, rx = (int)(31 * (double)w / W + 1e-3) + 3;
+  if ((ry < h ? ry : h) > kUpTR || (rx < w ? rx : w) > kUpTX) return 0;
+  return (int64_t)N * ((H + kUpRows - 1) / kUpRows) <= 65535 && (W + 31) / 32 <= 65535;
+}
+
+static void upsample_add_image_v2_launch(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top,
+                                         int64_t S, int64_t row0, void *image, int N, int C, int H, int W, int h, int w, int oexp,
+                                         void *stream) {
+  const int HB = (H + kUpRows - 1) / kUpRows;
+  const dim3 grid(C / 64, (W + 31) / 32, N * HB);
+  if (S > 0)
+    hipLaunchKernelGGL(upsample_add_image_v2_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, lateral, top, image, N, C, H, W, h,
+                       w, lat_scale, lat_shift, ldexpf(1.f, oexp), HB, (long long)S, (long long)row0);
+  else
+    hipLaunchKernelGGL(upsample_add_image_v2_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, lateral, top, image, N, C, H, W, h,
+                       w, lat_scale, lat_shift, ldexpf(1.f, oexp), HB, 0ll, 0ll);
+}
+
+/* dvis_upsample_add_image with `top` read where it lies in a token-major tensor: (N, S, C) floats, the map's h * w tokens at rows
+ * [row0, row0 + h * w) of every frame, one token = C contiguous floats (the finest level of the encoder memory).  Served by the
+ * second form only: shapes with dvis_upsample_add_image_v2_supported.  The same bytes as dvis_upsample_add_image on the (N, C, h, w)
+ * transpose of those rows. */
+DVIS_EXPORT int dvis_upsample_add_image_tokens(const float *lateral, const float *lat_scale, const float *lat_shift, const float *tokens,
+                                               int64_t S, int64_t row0, void *image, int N, int C, int H, int W, int h, int w, int oexp,
+                                               void *stream) {
+  DVIS_REQUIRE(lateral && tokens && image, "dvis_upsample_add_image_tokens: null pointer");
+  DVIS_REQUIRE((lat_scale == nullptr) == (lat_shift == nullptr), "dvis_upsample_add_image_tokens: scale and shift together");
+  DVIS_REQUIRE(dvis_upsample_add_image_v2_supported(N, C, H, W, h, w), "dvis_upsample_add_image_tokens: (N %d, C %d, %d x %d <- %d x %d) is "
+               "not served (C %% 64 == 0, W %% 4 == 0, up-sampling by about 2 or more)", N, C, H, W, h, w);
+  DVIS_REQUIRE(S > 0 && row0 >= 0 && row0 + (int64_t)h * w <= S, "dvis_upsample_add_image_tokens: rows [%lld, %lld) outside the %lld "
+               "tokens of a frame", (long long)row0, (long long)(row0 + (int64_t)h * w), (long long)S);
+  DVIS_REQUIRE((uintptr_t)lateral % 16 == 0 && (uintptr_t)tokens % 16 == 0, "dvis_upsample_add_image_tokens: lateral and tokens must be "
+               "16-byte aligned");
+  DVIS_REQUIRE((uintptr_t)image % 16 == 0 && dvis_conv_x3_image_bytes(N, C, H, W) < ((int64_t)1 << 31), "dvis_upsample_add_image_tokens: a "
+               "16-byte aligned image below 2 GiB");
+  upsample_add_image_v2_launch(lateral, lat_scale, lat_shift, tokens, S, row0, image, N, C, H, W, h, w, oexp, stream);
+  return dvis_check_launch("dvis_upsample_add_image_tokens");
+}
+
 DVIS_EXPORT int dvis_upsample_add_image(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top, void *image,
                                         int N, int C, int H, int W, int h, int w, int oexp, void *stream) {
   DVIS_REQUIRE(lateral && top && image, "dvis_upsample_add_image: null pointer");
@@ -455,6 +643,11 @@ DVIS_EXPORT int dvis_upsample_add_image(const float *lateral, const float *lat_s
   DVIS_REQUIRE(N > 0 && C > 0 && C % 64 == 0 && H > 0 && W > 0 && h > 0 && w > 0, "dvis_upsample_add_image: bad sizes");
   DVIS_REQUIRE((uintptr_t)image % 16 == 0 && dvis_conv_x3_image_bytes(N, C, H, W) < ((int64_t)1 << 31), "dvis_upsample_add_image: a 16-byte "
                "aligned image below 2 GiB");
+  if (__atomic_load_n(&g_upsample_v2, __ATOMIC_RELAXED) && (uintptr_t)lateral % 16 == 0 &&
+      dvis_upsample_add_image_v2_supported(N, C, H, W, h, w)) {
+    upsample_add_image_v2_launch(lateral, lat_scale, lat_shift, top, 0, 0, image, N, C, H, W, h, w, oexp, stream);
+    return dvis_check_launch("dvis_upsample_add_image");
+  }
   const int per = 16 * 65535 / H;    // images per launch: the grid's z extent is the image rows / 16
   DVIS_REQUIRE(per >= 1 && (W + 31) / 32 <= 65535, "dvis_upsample_add_image: map too large (%d x %d)", H, W);
   for (int i = 0; i < N; i += per) {

@@ -47,10 +47,9 @@ namespace {
 // Activation fragments of a wave's 32 tokens for K = 16 * KS, natural k order: lane (token j, half g) holds
 // x[token][16 S + 8 g + 0..7] for k-step S.
 // addp: NULL or the row of an embedding added in front of the split (x + pos is never written).
+// load_x_at: the same with the lane's row given by its address (`p` = the row + 8 g).
 template <int KS>
-__device__ __forceinline__ void load_x(const float *x, int64_t ldx, int64_t row, int g, float s, h8 *xh, h8 *xl,
-                                       const float *addp = nullptr) {
-  const float *p = x + row * ldx + 8 * g;
+__device__ __forceinline__ void load_x_at(const float *p, float s, h8 *xh, h8 *xl, const float *addp = nullptr) {
   f4 raw[2 * KS];
 #pragma unroll
   for (int S = 0; S < KS; ++S) raw[2 * S] = *(const f4 *)(p + 16 * S), raw[2 * S + 1] = *(const f4 *)(p + 16 * S + 4);
@@ -60,6 +59,28 @@ __device__ __forceinline__ void load_x(const float *x, int64_t ldx, int64_t row,
   }
 #pragma unroll
   for (int S = 0; S < KS; ++S) split8(raw[2 * S], raw[2 * S + 1], s, xh[S], xl[S]);
+}
+template <int KS>
+__device__ __forceinline__ void load_x(const float *x, int64_t ldx, int64_t row, int g, float s, h8 *xh, h8 *xl,
+                                       const float *addp = nullptr) {
+  load_x_at<KS>(x + row * ldx + 8 * g, s, xh, xl, addp);
+}
+
+// Two-level row address (ROWS: dvis_x3_linear_rows / dvis_x3_linear_add_rows): row r of the call lies at
+// (r / rows_per_batch) * batch_stride + (r % rows_per_batch) * ldx — one level's rows of every frame of a (frames, S, K) tensor,
+// read where they lie.  Per lane: a wave's 32 rows may straddle two frames.  r < M < 2^31, so the division is a 32-bit one.
+struct X3Rows {
+  unsigned rows_per_batch;
+  int64_t batch_stride;
+};
+template <bool ROWS>
+__device__ __forceinline__ const float *x3_row(const float *x, int64_t ldx, int64_t row, X3Rows rm) {
+  if constexpr (ROWS) {
+    const unsigned b = (unsigned)row / rm.rows_per_batch;
+    return x + (int64_t)b * rm.batch_stride + (int64_t)((unsigned)row - b * rm.rows_per_batch) * ldx;
+  } else {
+    return x + row * ldx;
+  }
 }
 
 // Row-contiguous stores of one 32-feature block: the lane-per-token accumulator quads go through the wave's 4 KB of LDS
@@ -214,10 +235,11 @@ __device__ __forceinline__ void epilogue(f16v *acc, const EpiArgs &e, const floa
 // ---------------------------------------------------------------------------------------------------------------------
 // out (M x 32 NB npass) = act( x (M x K) W^T * inv + bias ) at K = 256: one projection, its output features in `npass` passes of
 // 32 NB over the same activation fragments.  Weight stream: [pass][K / 32 items of 2 k-steps x NB blocks].
-template <int NB>
+template <int NB, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void x3_linear_kernel(const float *__restrict__ x, int64_t ldx, int64_t M,
                                                              const void *__restrict__ wp, float xscale, int npass,
-                                                             const float *__restrict__ xadd, int64_t xadd_rows, EpiArgs e) {
+                                                             const float *__restrict__ xadd, int64_t xadd_rows, EpiArgs e,
+                                                             X3Rows rm) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   constexpr int K = 256, KS = K / 16, NI = K / 32;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, g = lane >> 5;
@@ -235,7 +257,7 @@ __global__ __launch_bounds__(kThreads) void x3_linear_kernel(const float *__rest
     const int64_t tok0 = tile * kTileTok + wave * 32;
     const int64_t row = tok0 + j < M ? tok0 + j : M - 1;
     h8 xh[KS], xl[KS];
-    load_x<KS>(x, ldx, row, g, xscale, xh, xl, xadd ? xadd + (row % xadd_rows) * K + 8 * g : nullptr);
+    load_x_at<KS>(x3_row<ROWS>(x, ldx, row, rm) + 8 * g, xscale, xh, xl, xadd ? xadd + (row % xadd_rows) * K + 8 * g : nullptr);
     for (int pass = 0; pass < npass; ++pass) {
       f16v acc[NB];
 #pragma unroll
@@ -264,10 +286,11 @@ __global__ __launch_bounds__(kThreads) void x3_linear_kernel(const float *__rest
 // rows and the embedding's rows are then fetched 32 k at a time (4 + 4 loads in flight: the same eight as the plain form's chunk).
 constexpr int x3_stream_layout_blocks(int nb) { return 4 * nb % 8 == 0 ? nb : nb + 1; }
 
-template <int NB, bool LN, bool EX = false, bool ADD = false>
+template <int NB, bool LN, bool EX = false, bool ADD = false, bool ROWS = false>
 __global__ __launch_bounds__(512) void x3_linear_stream_kernel(const float *__restrict__ x, int64_t ldx, int64_t M, int K,
                                                                const void *__restrict__ wp, float xscale, int npass,
-                                                               const float *__restrict__ xadd, int64_t xadd_rows, EpiArgs e) {
+                                                               const float *__restrict__ xadd, int64_t xadd_rows, EpiArgs e,
+                                                               X3Rows rm) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   constexpr int NBL = x3_stream_layout_blocks(NB);
   constexpr int NW = 8, PW = 4 * NBL / NW, kTile = NW * 32;
@@ -309,12 +332,12 @@ __global__ __launch_bounds__(512) void x3_linear_stream_kernel(const float *__re
       }
     };
     int64_t r0 = row_of(blockIdx.x);
-    const float *rowp = x + r0 * ldx + 8 * g, *posp = xadd + (r0 % xadd_rows) * K + 8 * g;
+    const float *rowp = x3_row<ROWS>(x, ldx, r0, rm) + 8 * g, *posp = xadd + (r0 % xadd_rows) * K + 8 * g;
     load_raw(rowp, posp, 0);
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
       const int64_t tok0 = tile * kTile + wave * 32;
       const int64_t rn = row_of(tile + gridDim.x < ntiles ? tile + gridDim.x : tile);
-      const float *nrowp = x + rn * ldx + 8 * g, *nposp = xadd + (rn % xadd_rows) * K + 8 * g;
+      const float *nrowp = x3_row<ROWS>(x, ldx, rn, rm) + 8 * g, *nposp = xadd + (rn % xadd_rows) * K + 8 * g;
       for (int pass = 0; pass < npass; ++pass) {
         f16v acc[NB];
 #pragma unroll
@@ -349,7 +372,7 @@ __global__ __launch_bounds__(512) void x3_linear_stream_kernel(const float *__re
 #pragma unroll
     for (int s = 0; s < 4; ++s) raw[2 * s] = *(const f4 *)(rowp + 64 * kc + 16 * s), raw[2 * s + 1] = *(const f4 *)(rowp + 64 * kc + 16 * s + 4);
   };
-  auto row_ptr = [&](int64_t tile) { return x + row_of(tile) * ldx + 8 * g; };
+  auto row_ptr = [&](int64_t tile) { return x3_row<ROWS>(x, ldx, row_of(tile), rm) + 8 * g; };
   const float *rowp = row_ptr(blockIdx.x);
   load_raw(rowp, 0);
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -608,7 +631,7 @@ DVIS_EXPORT int dvis_x3_pack(const float *w, int64_t ldw, int N, int K, int wexp
 
 static int x3_linear_impl(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *xadd,
                           int64_t xadd_rows, const float *bias, int relu, float *out, int64_t ldo, void *stream,
-                          const float *radd = nullptr, int64_t ldr = 0);
+                          const float *radd = nullptr, int64_t ldr = 0, int64_t rows_per_batch = 0, int64_t batch_stride = 0);
 
 DVIS_EXPORT int dvis_x3_linear(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp,
                                const float *bias, int relu, float *out, int64_t ldo, void *stream) {
@@ -631,9 +654,40 @@ DVIS_EXPORT int dvis_x3_linear_res(const float *x, int64_t ldx, int64_t M, int K
   return x3_linear_impl(x, ldx, M, K, wp, N, xexp, wexp, nullptr, 0, bias, act, out, ldo, stream, res, ldres);
 }
 
+// The two-level row address: every offset the kernels form stays inside the operand the caller describes, and that is checked
+// to lie below 2^40 floats (no 32-bit offsets are involved: the rows are addressed by pointer).
+static int x3_check_rows(const char *what, int64_t ldx, int64_t M, int K, int64_t rows_per_batch, int64_t batch_stride) {
+  DVIS_REQUIRE(rows_per_batch > 0 && rows_per_batch < ((int64_t)1 << 31) && M % rows_per_batch == 0,
+               "%s: M = %lld must be a whole number of batches of rows_per_batch = %lld rows", what, (long long)M, (long long)rows_per_batch);
+  DVIS_REQUIRE(ldx >= K, "%s: row stride %lld below K = %d", what, (long long)ldx, K);
+  DVIS_REQUIRE(batch_stride % 4 == 0 && batch_stride >= rows_per_batch * ldx && batch_stride < ((int64_t)1 << 40),
+               "%s: batch_stride = %lld must be a multiple of 4 floats and at least rows_per_batch * ldx", what, (long long)batch_stride);
+  return DVIS_OK;
+}
+
+DVIS_EXPORT int dvis_x3_linear_rows(const float *x, int64_t ldx, int64_t rows_per_batch, int64_t batch_stride, int64_t M, int K,
+                                    const void *wp, int N, int xexp, int wexp, const float *bias, int relu, float *out, int64_t ldo,
+                                    void *stream) {
+  const int rc = x3_check_rows("dvis_x3_linear_rows", ldx, M, K, rows_per_batch, batch_stride);
+  if (rc != DVIS_OK) return rc;
+  DVIS_REQUIRE(relu == 0 || relu == 1, "dvis_x3_linear_rows: relu must be 0 or 1");
+  return x3_linear_impl(x, ldx, M, K, wp, N, xexp, wexp, nullptr, 0, bias, relu, out, ldo, stream, nullptr, 0, rows_per_batch, batch_stride);
+}
+
+DVIS_EXPORT int dvis_x3_linear_add_rows(const float *x, int64_t ldx, int64_t rows_per_batch, int64_t batch_stride, int64_t M, int K,
+                                        const void *wp, int N, int xexp, int wexp, const float *xadd, int64_t xadd_rows,
+                                        const float *bias, int relu, float *out, int64_t ldo, void *stream) {
+  const int rc = x3_check_rows("dvis_x3_linear_add_rows", ldx, M, K, rows_per_batch, batch_stride);
+  if (rc != DVIS_OK) return rc;
+  DVIS_REQUIRE(relu == 0 || relu == 1, "dvis_x3_linear_add_rows: relu must be 0 or 1");
+  DVIS_REQUIRE(xadd && xadd_rows > 0 && (uintptr_t)xadd % 16 == 0, "dvis_x3_linear_add_rows: xadd (xadd_rows x K, 16-byte aligned) is required");
+  DVIS_REQUIRE(K == 256 && dvis_x3_linear_supported(N, K, 0), "dvis_x3_linear_add_rows: served for K = 256 (N %d, K %d)", N, K);
+  return x3_linear_impl(x, ldx, M, K, wp, N, xexp, wexp, xadd, xadd_rows, bias, relu, out, ldo, stream, nullptr, 0, rows_per_batch, batch_stride);
+}
+
 static int x3_linear_impl(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *xadd,
                           int64_t xadd_rows, const float *bias, int relu, float *out, int64_t ldo, void *stream, const float *radd,
-                          int64_t ldr) {
+                          int64_t ldr, int64_t rows_per_batch, int64_t batch_stride) {
   DVIS_REQUIRE(dvis_x3_linear_supported(N, K, 0), "dvis_x3_linear: (N, K) = (%d, %d) is not served (K %% 64 == 0; N in 128 / 192 / 256 or N %% 256 == 0; N = 288 at K = 256)", N, K);
   const int rc = x3_check_common(x, ldx, M, wp, out, ldo);
   if (rc != DVIS_OK) return rc;
@@ -647,36 +701,43 @@ static int x3_linear_impl(const float *x, int64_t ldx, int64_t M, int K, const v
   hipStream_t st = (hipStream_t)stream;
   int NB;
   const int npass = x3_passes(N, &NB);
-#define DVIS_X3_STREAM_FORM(NBV, LNV, EXV, ADDV, XADD, XROWS, WHAT, LDS_EXTRA)                                        \
+  const bool rows = rows_per_batch > 0;      // the two-level row address (dvis_x3_linear_rows / _add_rows)
+  const X3Rows rm = {(unsigned)rows_per_batch, batch_stride};
+#define DVIS_X3_STREAM_FORM(NBV, LNV, EXV, ADDV, ROWSV, XADD, XROWS, WHAT, LDS_EXTRA)                                      \
   {                                                                                                                  \
     static DvisLdsOptIn opted;                                                                                       \
     typedef Ring<4 * x3_stream_layout_blocks(NBV) / 8, 8, 8> R;                                                      \
     const size_t lds_bytes = kStages * R::kItemBytes + 8 * kScratch + (LDS_EXTRA);                                   \
-    const int rc2 = dvis_lds_opt_in((const void *)x3_linear_stream_kernel<NBV, LNV, EXV, ADDV>, lds_bytes, &opted, WHAT);  \
+    const int rc2 = dvis_lds_opt_in((const void *)x3_linear_stream_kernel<NBV, LNV, EXV, ADDV, ROWSV>, lds_bytes, &opted, WHAT);  \
     if (rc2 != DVIS_OK) return rc2;                                                                                  \
     const int64_t ntiles = (M + 255) / 256;                                                                          \
-    hipLaunchKernelGGL((x3_linear_stream_kernel<NBV, LNV, EXV, ADDV>), dim3(x3_grid(ntiles)), dim3(512), lds_bytes, st, x, ldx, M, K, wp, \
-                       xs, npass, XADD, XROWS, e);                                                                   \
+    hipLaunchKernelGGL((x3_linear_stream_kernel<NBV, LNV, EXV, ADDV, ROWSV>), dim3(x3_grid(ntiles)), dim3(512), lds_bytes, st, x, ldx, M, K, wp, \
+                       xs, npass, XADD, XROWS, e, rm);                                                               \
     return dvis_check_launch(WHAT);                                                                                  \
   }
-#define DVIS_X3_STREAM_EX(NBV, LNV, EXV, WHAT, LDS_EXTRA) DVIS_X3_STREAM_FORM(NBV, LNV, EXV, false, (const float *)nullptr, (int64_t)0, WHAT, LDS_EXTRA)
+#define DVIS_X3_STREAM_EX(NBV, LNV, EXV, WHAT, LDS_EXTRA) DVIS_X3_STREAM_FORM(NBV, LNV, EXV, false, false, (const float *)nullptr, (int64_t)0, WHAT, LDS_EXTRA)
 #define DVIS_X3_STREAM(NBV, LNV, WHAT, LDS_EXTRA) DVIS_X3_STREAM_EX(NBV, LNV, false, WHAT, LDS_EXTRA)
-#define DVIS_X3_RESIDENT(NBV)                                                                                        \
+#define DVIS_X3_RESIDENT(NBV, ROWSV)                                                                                 \
   {                                                                                                                  \
     static DvisLdsOptIn opted;                                                                                       \
-    return x3_launch(x3_linear_kernel<NBV>, &opted, kStages * Ring<NBV>::kItemBytes + kWaves * kScratch + (size_t)N * 4, \
-                     M, st, "dvis_x3_linear", x, ldx, M, wp, xs, npass, xadd, xadd_rows, e);                         \
+    return x3_launch(x3_linear_kernel<NBV, ROWSV>, &opted, kStages * Ring<NBV>::kItemBytes + kWaves * kScratch + (size_t)N * 4, \
+                     M, st, "dvis_x3_linear", x, ldx, M, wp, xs, npass, xadd, xadd_rows, e, rm);                     \
   }
   if (relu == 2 || radd) {      // GELU / residual epilogue: the ViT blocks' shapes (N a multiple of 256)
     DVIS_REQUIRE(NB == 8 && !xadd, "dvis_x3_linear_res: the GELU / residual epilogue is served for N %% 256 == 0 (N = %d)", N);
     DVIS_X3_STREAM_EX(8, false, true, "dvis_x3_linear_res", (size_t)N * 4)
   }
+  if (rows) {      // rows read in place: the N % 256 == 0 instances (all the decoder's K / V projections need)
+    DVIS_REQUIRE(NB == 8 && relu != 2 && !radd, "dvis_x3_linear_rows: served for N %% 256 == 0 (N = %d)", N);
+    if (xadd) DVIS_X3_RESIDENT(8, true)
+    DVIS_X3_STREAM_FORM(8, false, false, false, true, (const float *)nullptr, (int64_t)0, "dvis_x3_linear_rows", (size_t)N * 4)
+  }
   if (xadd) {      // the embedding is added while the row's fragments are built (K = 256)
     switch (NB) {
-      case 4: DVIS_X3_RESIDENT(4)
-      case 6: DVIS_X3_RESIDENT(6)
-      case 8: DVIS_X3_RESIDENT(8)
-      default: DVIS_X3_STREAM_FORM(9, false, false, true, xadd, xadd_rows, "dvis_x3_linear_add", (size_t)N * 4)
+      case 4: DVIS_X3_RESIDENT(4, false)
+      case 6: DVIS_X3_RESIDENT(6, false)
+      case 8: DVIS_X3_RESIDENT(8, false)
+      default: DVIS_X3_STREAM_FORM(9, false, false, true, false, xadd, xadd_rows, "dvis_x3_linear_add", (size_t)N * 4)
     }
   }
   switch (NB) {
@@ -707,6 +768,7 @@ DVIS_EXPORT int dvis_x3_linear_ln(const float *x, int64_t ldx, int64_t M, int K,
   e.flag = gd.flag, e.tag = gd.tag;
   const float xs = x3_pow2(xexp);
   const int npass = 1;
+  const X3Rows rm = {};
   hipStream_t st = (hipStream_t)stream;
   DVIS_X3_STREAM(8, true, "dvis_x3_linear_ln", (size_t)3 * 256 * 4)
 #undef DVIS_X3_STREAM

@@ -2082,12 +2082,50 @@ def _x3_rows(x, name):
     return x2, ld
 
 
+X3_LINEAR_ROWS = os.environ.get("DVIS_X3_LINEAR_ROWS", "1") != "0"
+
+
+def x3_rows_in_place(x, N):
+    """Is ``x`` a (B, S, K) slice of a longer (B, S', K) tensor — unit inner stride, row stride K, a batch stride that is a multiple
+    of 4 floats — whose rows dvis_x3_linear_rows / _add_rows read where they lie (N % 256 == 0)?  Otherwise, and with
+    DVIS_X3_LINEAR_ROWS=0, ``x3_linear`` compacts such a view first."""
+    return (X3_LINEAR_ROWS and x.dim() == 3 and not x.is_contiguous() and x.shape[0] > 0 and x.shape[1] > 0 and N % 256 == 0
+            and x.stride(2) == 1 and x.stride(1) == x.shape[2] and x.stride(0) % 4 == 0 and x.stride(0) >= x.shape[1] * x.shape[2]
+            and x.data_ptr() % 16 == 0)
+
+
+def _x3_linear_rows(x, weight, bias, relu, xexp, xadd):
+    N, K = weight.shape
+    B, S, _ = x.shape
+    buf, wexp = x3_pack(weight)
+    out = torch.empty((B, S, N), dtype=torch.float32, device=x.device)
+    lib = native.lib()
+    bptr = None if bias is None else native.dev_ptr(bias.detach(), "bias")
+    xe = X3_XEXP if xexp is None else xexp
+    with torch.cuda.device(x.device):
+        if xadd is not None:
+            if xadd.numel() != S * K or xadd.dtype != torch.float32 or not xadd.is_cuda:
+                raise RuntimeError("x3_linear: xadd must be a float32 GPU (S, K) embedding for x of shape (B, S, K)")
+            xadd = xadd.contiguous()
+            native.check(lib.dvis_x3_linear_add_rows(
+                ctypes.c_void_p(x.data_ptr()), K, S, x.stride(0), B * S, K, ctypes.c_void_p(buf.data_ptr()), N, xe, wexp,
+                ctypes.c_void_p(xadd.data_ptr()), S, bptr, int(relu), ctypes.c_void_p(out.data_ptr()), N,
+                native.stream_ptr(x.device)), "dvis_x3_linear_add_rows")
+        else:
+            native.check(lib.dvis_x3_linear_rows(
+                ctypes.c_void_p(x.data_ptr()), K, S, x.stride(0), B * S, K, ctypes.c_void_p(buf.data_ptr()), N, xe, wexp,
+                bptr, int(relu), ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device)), "dvis_x3_linear_rows")
+    return out
+
+
 def x3_linear(x, weight, bias, relu=False, xexp=None, xadd=None, act=None, residual=None):
     """``relu?((x + xadd) @ weight.T + bias)`` through dvis_x3_linear[_add]; with act ("gelu" | "relu" | None) / residual:
     ``act(x @ weight.T + bias) + residual`` through dvis_x3_linear_res (GELU and the residual add inside the GEMM's epilogue).  x (..., K) float32 GPU; weight (N, K); xadd: None or
     a (1, S, 256) / (S, 256) embedding for x of shape (B, S, 256), broadcast over B — added inside the kernel while it builds the
     row's fragments, the sum is never written (K = 256, any N the kernels serve: all passes over N run from one read of the row)."""
     N, K = weight.shape
+    if act is None and residual is None and x3_rows_in_place(x, N):
+        return _x3_linear_rows(x, weight, bias, relu, xexp, xadd)
     x2, ldx = _x3_rows(x, "x")
     buf, wexp = x3_pack(weight)
     out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
@@ -2504,12 +2542,37 @@ def _image_chunks(N, C, K, H, W, OH, OW):
     return max(1, min(N, (2 ** 31 - 1) // per))
 
 
+def _token_major_rows(top):
+    """``top`` (N, C, h, w) as a view of token-major rows — ``tokens[:, r : r + h * w].transpose(1, 2).reshape(N, C, h, w)`` of an
+    (N, S, C) tensor: S (h * w for a single frame), or 0 when it is anything else."""
+    N, C, h, w = top.shape
+    if not (top.stride(1) == 1 and top.stride(3) == C and top.stride(2) == w * C and top.data_ptr() % 16 == 0):
+        return 0
+    if N == 1:
+        return h * w
+    return top.stride(0) // C if top.stride(0) % C == 0 and top.stride(0) >= h * w * C else 0
+
+
+def upsample_add_image_reads_tokens(lateral, top):
+    """Does ``upsample_add_image`` read this ``top`` where it lies (dvis_upsample_add_image_tokens)?  A token-major view
+    (``_token_major_rows``), a shape the second kernel form serves, and that form switched on (DVIS_UPSAMPLE_IMAGE_V2)."""
+    N, C, H, W = lateral.shape
+    lib = native.lib()
+    return bool(lateral.is_cuda and top.is_cuda and top.dtype == torch.float32 and not top.is_contiguous() and _token_major_rows(top)
+                and lateral.data_ptr() % 16 == 0 and lib.dvis_upsample_add_image_set_v2(-1)
+                and lib.dvis_upsample_add_image_v2_supported(N, C, H, W, top.shape[-2], top.shape[-1]))
+
+
 def upsample_add_image(lateral, top, lat_affine=None, oexp=None):
-    """`upsample_add` with the sum written as an operand image (the 3x3 output convolution behind it reads fragments)."""
+    """`upsample_add` with the sum written as an operand image (the 3x3 output convolution behind it reads fragments).  ``top``:
+    an (N, C, h, w) map, or a token-major view of one (``upsample_add_image_reads_tokens``: read in place; any other strided
+    view is copied)."""
     N, C, H, W = lateral.shape
     lib = native.lib()
     oe = X3_CONV_XEXP if oexp is None else oexp
-    top = top.contiguous()
+    S = _token_major_rows(top) if upsample_add_image_reads_tokens(lateral, top) else 0
+    if not S:
+        top = top.contiguous()
     data = torch.empty(lib.dvis_conv_x3_image_bytes(N, C, H, W), dtype=torch.uint8, device=lateral.device)
     img = OperandImage(data, N, C, H, W, oe)
     step = _image_chunks(N, C, C, H, W, H, W)
@@ -2518,6 +2581,12 @@ def upsample_add_image(lateral, top, lat_affine=None, oexp=None):
             n = min(step, N - i)
             sc = None if lat_affine is None else native.dev_ptr(lat_affine[0].reshape(N, C)[i:i + n], "scale")
             sh = None if lat_affine is None else native.dev_ptr(lat_affine[1].reshape(N, C)[i:i + n], "shift")
+            if S:
+                native.check(lib.dvis_upsample_add_image_tokens(
+                    native.dev_ptr(lateral[i:i + n], "lateral"), sc, sh, ctypes.c_void_p(top[i:i + n].data_ptr()), S, 0,
+                    ctypes.c_void_p(img.images(i, n).data_ptr()), n, C, H, W, top.shape[-2], top.shape[-1], oe,
+                    native.stream_ptr(lateral.device)), "dvis_upsample_add_image_tokens")
+                continue
             native.check(lib.dvis_upsample_add_image(native.dev_ptr(lateral[i:i + n], "lateral"), sc, sh, native.dev_ptr(top[i:i + n], "top"),
                                                      ctypes.c_void_p(img.images(i, n).data_ptr()), n, C, H, W, top.shape[-2], top.shape[-1], oe,
                                                      native.stream_ptr(lateral.device)), "dvis_upsample_add_image")

@@ -115,6 +115,8 @@ SIGNATURES = {
     "dvis_x3_tile_linear": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _i, _p, _i64, _p, _i64, _p]),
     "dvis_x3_linear_res": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _i, _p, _i64, _p, _i64, _p]),
     "dvis_x3_linear_add": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _i64, _p, _i, _p, _i64, _p]),
+    "dvis_x3_linear_rows": (_i, [_p, _i64, _i64, _i64, _i64, _i, _p, _i, _i, _i, _p, _i, _p, _i64, _p]),
+    "dvis_x3_linear_add_rows": (_i, [_p, _i64, _i64, _i64, _i64, _i, _p, _i, _i, _i, _p, _i64, _p, _i, _p, _i64, _p]),
     "dvis_x3_linear_ln": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _p, _i64, _p, _p, _f, _p, _i64, _p, _p, _i64, _p]),
     "dvis_x3_ffn_packed_bytes": (_i64, [_i, _i, _i]),
     "dvis_x3_ffn_pack": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _i, _i, _p, _p]),
@@ -138,6 +140,9 @@ SIGNATURES = {
     "dvis_conv_x3_pack_image": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "dvis_conv_x3_image": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
     "dvis_upsample_add_image": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "dvis_upsample_add_image_v2_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "dvis_upsample_add_image_set_v2": (_i, [_i]),
+    "dvis_upsample_add_image_tokens": (_i, [_p, _p, _p, _p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dvis_gemm_num_configs": (_i, []),
     "dvis_gemm_pick_config": (_i, [_i, _i, _i, _i]),
     "dvis_gemm_pick_config_nw": (_i, [_i, _i, _i, _i, _i]),

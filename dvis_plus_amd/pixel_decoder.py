@@ -579,13 +579,11 @@ class MSDeformAttnPixelDecoder(nn.Module):
             with Fn.x3_stage("encoder"):
                 y, _, _, shapes_py = self.transformer(srcs, pos, affines)
             bs = y.shape[0]
-            out, tokens, start = [], [], 0
+            memory, out, tokens, start = y, [], [], 0
             for li, (h, w) in enumerate(shapes_py):
                 tokens.append(y[:, start:start + h * w])
-                if li + 1 == len(shapes_py) and self.num_fpn_levels > 0:
-                    out.append(Fn.tokens_to_map(y, start, h, w))    # the FPN's top-down path reads this one: a real map
-                else:
-                    out.append(tokens[-1].transpose(1, 2).reshape(bs, -1, h, w))  # a strided view, no copy
+                out.append(tokens[-1].transpose(1, 2).reshape(bs, -1, h, w))  # a strided view, no copy
+                finest = (start, h, w)      # (the FPN's top-down path reads the last one: in place where the kernel can)
                 start += h * w
             with Fn.x3_stage("mask_path"):        # lateral 1x1 -> top-down add -> 3x3 output conv -> mask_features 1x1
                 deferred = None            # the last output convolution's GroupNorm + ReLU, left to mask_features' load path
@@ -593,8 +591,11 @@ class MSDeformAttnPixelDecoder(nn.Module):
                     x = features[f].float().contiguous()      # NCHW for the fused FPN path (no-op for the R50's maps)
                     cur_fpn, affine = self.lateral_convs[idx].conv_and_affine(x)    # GroupNorm applied inside upsample_add
                     oc = self.output_convs[idx]
-                    if cur_fpn.is_cuda and cur_fpn.dtype == torch.float32 and cur_fpn.is_contiguous() and out[-1].dtype == torch.float32 \
-                            and oc.image_input_ok(*cur_fpn.shape, cur_fpn.device):
+                    as_image = cur_fpn.is_cuda and cur_fpn.dtype == torch.float32 and cur_fpn.is_contiguous() \
+                        and out[-1].dtype == torch.float32 and oc.image_input_ok(*cur_fpn.shape, cur_fpn.device)
+                    if idx == 0 and not (as_image and Fn.upsample_add_image_reads_tokens(cur_fpn, out[-1])):
+                        out[-1] = Fn.tokens_to_map(memory, *finest)      # a real map for the kernels that read NCHW
+                    if as_image:
                         # the top-down sum as an operand image: the 3x3 output convolution reads pre-split fragments (csrc/conv1x1_x3.hip)
                         # out[-1] of the LAST level past the multi-scale features has one reader, mask_features: its normalisation
                         # can wait for that read (an inner level's is read by the next upsample_add, a multi-scale map by the decoder)

@@ -307,7 +307,10 @@ class _MaskedDecoderBase(nn.Module):
                     pos_t = self.pe_layer.compute(h, w, tok.device).flatten(2).transpose(1, 2)      # (1, hw, C)
                     if Fn.x3_on() and Fn.x3_ok(tok, Wk.shape[0], Wk.shape[1], add=True):
                         # every pixel's keys / values for all layers of the level: split-f16 matrix-core GEMM (csrc/gemm_x3.hip)
-                        tok = tok.contiguous()          # a level's rows of the encoder memory: ONE compaction serves both projections
+                        # a level's rows of the encoder memory are read where they lie (dvis_x3_linear_rows); where that entry
+                        # does not serve the view, ONE compaction serves both projections
+                        if not Fn.x3_rows_in_place(tok, Wk.shape[0]):
+                            tok = tok.contiguous()
                         kall = Fn.x3_linear(tok, Wk, bk, xadd=pos_t + le).transpose(0, 1)   # (the (N, hw, C) sum is never written)
                         vall = Fn.x3_linear(tok, Wv, bv_le).transpose(0, 1)
                     else:

@@ -680,6 +680,16 @@ int dvis_x3_linear(const float *x, int64_t ldx, int64_t M, int K, const void *pa
  * video_mask2former_transformer_decoder.py:81-88.  K = 256 (the row's fragments stay in registers for every pass over N). */
 int dvis_x3_linear_add(const float *x, int64_t ldx, int64_t M, int K, const void *packed, int N, int xexp, int wexp,
                        const float *xadd, int64_t xadd_rows, const float *bias, int relu, float *out, int64_t ldo, void *stream);
+/* dvis_x3_linear / dvis_x3_linear_add on rows read WHERE THEY LIE in a (batches, S, K) tensor: row r of the call (0 <= r < M,
+ * M a whole number of batches) is at x + (r / rows_per_batch) * batch_stride + (r % rows_per_batch) * ldx floats — one level's rows
+ * of every frame of the encoder memory, without the compaction a single row stride needs.  batch_stride % 4 == 0 and
+ * >= rows_per_batch * ldx; xadd's row stays r mod xadd_rows; out is M x N with the single stride ldo.  The same summation order per
+ * row as the single-stride entries (the same bits).  Served for N % 256 == 0 (K = 256 for the _add form). */
+int dvis_x3_linear_rows(const float *x, int64_t ldx, int64_t rows_per_batch, int64_t batch_stride, int64_t M, int K, const void *packed,
+                        int N, int xexp, int wexp, const float *bias, int relu, float *out, int64_t ldo, void *stream);
+int dvis_x3_linear_add_rows(const float *x, int64_t ldx, int64_t rows_per_batch, int64_t batch_stride, int64_t M, int K,
+                            const void *packed, int N, int xexp, int wexp, const float *xadd, int64_t xadd_rows, const float *bias,
+                            int relu, float *out, int64_t ldo, void *stream);
 /* dvis_x3_linear with the activation chosen by `act` (0 none, 1 ReLU, 2 the exact GELU of nn.GELU(): 0.5 t (1 + erf(t / sqrt 2)))
  * and an optional residual added AFTER it: out = act(x W^T + bias) + res (res: M x N, row stride ldres floats, 16-byte aligned; may
  * alias nothing the kernel writes).  The ViT blocks of the DINOv2 / ViT-Adapter backbones (mask2former/modeling/
@@ -814,6 +824,16 @@ int dvis_conv_x3_image(const void *ximg, const float *x, const void *packed, con
                        double *gn_part);      /* gn_part: as dvis_conv1x1_x3 (image in, fp32 map out), or NULL */
 int dvis_upsample_add_image(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top, void *image, int N,
                             int C, int H, int W, int h, int w, int oexp, void *stream);
+/* dvis_upsample_add_image has two kernels that write the same bytes.  The second one (16-byte lateral loads, the block's top taps
+ * staged once in LDS, the fragments transposed through LDS) serves shapes with dvis_upsample_add_image_v2_supported — W % 4 == 0, a
+ * 16-byte aligned lateral, up-sampling by about 2 or more — unless DVIS_UPSAMPLE_IMAGE_V2=0 / dvis_upsample_add_image_set_v2(0); every
+ * other shape takes the first.  _set_v2 returns the previous setting (on < 0: reads it only).
+ * dvis_upsample_add_image_tokens: `top` read where it lies in a token-major (N, S, C) tensor, the map's h * w tokens at rows
+ * [row0, row0 + h * w) of every frame (the finest level of the encoder memory, never transposed to a map); v2-supported shapes only. */
+int dvis_upsample_add_image_v2_supported(int N, int C, int H, int W, int h, int w);
+int dvis_upsample_add_image_set_v2(int on);
+int dvis_upsample_add_image_tokens(const float *lateral, const float *lat_scale, const float *lat_shift, const float *tokens, int64_t S,
+                                   int64_t row0, void *image, int N, int C, int H, int W, int h, int w, int oexp, void *stream);
 int dvis_x3_ffn_pack(const float *W1, int64_t ldw1, const float *W2, int64_t ldw2, int K, int H, int N, int w1exp, int w2exp,
                      void *packed, void *stream);
 int dvis_x3_ffn_ln(const float *x, int64_t ldx, int64_t M, int K, int H, int N, const void *packed, int xexp, int w1exp,
