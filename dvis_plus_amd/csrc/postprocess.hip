@@ -304,24 +304,97 @@ __global__ __launch_bounds__(256) void resize2_kernel(
   }
 }
 
+// ---- the host plan: how each entry point cuts its work into workgroups and grid-stride sweeps, and which form of the semantic
+// arg-max serves a call.  The launches below and dvis_postprocess_plan both read it from here; nothing else holds a grid cap.
+constexpr int kBlock = 256;                    // threads per workgroup, every kernel of this file
+constexpr int kVssMaxC = 128;                  // class sums a thread (generic form) or a wave (MFMA form) holds
+constexpr size_t kArgmaxMaxBlocks = 256 * 16;  // vps / generic vss, one pixel per thread: bounds the global area atomics
+constexpr size_t kMfmaMaxBlocks = 256 * 9;     // MFMA vss: 4 waves per workgroup, one 32-pixel chunk per wave and sweep
+constexpr size_t kResizeMaxBlocks = 256 * 64;  // resize2 (one float per thread), resize2_gt0 (one 4-pixel group per thread)
+constexpr int kMfmaChunk = 32;                 // pixels per wave chunk (NT = 2 tiles of 16)
+constexpr int kMfmaLdsRow = 132;               // floats per class-matrix row in LDS (128 + 4 of padding)
+constexpr size_t kMfmaMaxLds = 64 * 1024;      // the MFMA form's gate: Q rows must fit the default dynamic LDS limit
+
+struct PostPlan {
+  int workgroups = 0, sweeps = 0;              // 0 / 0: nothing is launched (T == 0 or K == 0)
+  int mfma = 0, k4 = 0, identity2 = 0, lds_bytes = 0;      // dvis_vss_argmax only
+};
+
+// `items` work items, `per_block` of them per workgroup and sweep, at most `max_blocks` workgroups
+void plan_sweeps(PostPlan &p, size_t items, size_t per_block, size_t max_blocks) {
+  if (items == 0) return;
+  size_t blocks = (items + per_block - 1) / per_block;
+  if (blocks > max_blocks) blocks = max_blocks;
+  const size_t per_sweep = blocks * per_block;
+  p.workgroups = (int)blocks;
+  p.sweeps = (int)((items + per_sweep - 1) / per_sweep);
+}
+
+int plan_vps(PostPlan &p, int K, int T, int img_h, int img_w, int out_h, int out_w) {
+  DVIS_REQUIRE(K > 0 && K <= kMaxK && T >= 0 && img_h > 0 && img_w > 0 && out_h > 0 && out_w > 0,
+               "vps_argmax: bad sizes (K must be 1..%d)", kMaxK);
+  DVIS_REQUIRE((size_t)T * out_h * out_w < 0x7fffffffu, "vps_argmax: more than 2^31 output pixels");
+  plan_sweeps(p, (size_t)T * out_h * out_w, kBlock, kArgmaxMaxBlocks);
+  return DVIS_OK;
+}
+
+int plan_vss(PostPlan &p, int Q, int C, int cls_row_stride, int T, int img_h, int img_w, int out_h, int out_w) {
+  DVIS_REQUIRE(Q > 0 && C > 0 && C <= kVssMaxC && T >= 0 && img_h > 0 && img_w > 0 && out_h > 0 && out_w > 0,
+               "vss_argmax: bad sizes (C must be 1..%d)", kVssMaxC);
+  if (T == 0) return DVIS_OK;
+  DVIS_REQUIRE(cls_row_stride >= C && cls_row_stride % 32 == 0 && cls_row_stride <= kVssMaxC,
+               "vss_argmax: cls rows must be zero padded to a multiple of 32 floats (<= %d), 16-byte aligned", kVssMaxC);
+  const size_t npix = (size_t)T * out_h * out_w;
+  p.k4 = cls_row_stride / 4;                    // 8, 16, 24 or 32 float4 of class sums per thread
+  p.identity2 = img_h == out_h && img_w == out_w;
+  // GEMM form on the matrix cores: cls padded to 128 columns; Q % 4 == 0 so that no row past the matrix is read; Q rows in LDS
+  const size_t lds = (size_t)Q * kMfmaLdsRow * sizeof(float);
+  if (p.identity2 && cls_row_stride == 128 && Q % 4 == 0 && lds <= kMfmaMaxLds) {
+    p.mfma = 1;
+    p.lds_bytes = (int)lds;
+    plan_sweeps(p, (npix + kMfmaChunk - 1) / kMfmaChunk, 4, kMfmaMaxBlocks);
+  } else {
+    plan_sweeps(p, npix, kBlock, kArgmaxMaxBlocks);
+  }
+  return DVIS_OK;
+}
+
+int plan_resize2(PostPlan &p, const char *name, int K, int T, int img_h, int img_w, int out_h, int out_w, int per_thread) {
+  DVIS_REQUIRE(K >= 0 && T >= 0 && img_h > 0 && img_w > 0 && out_h > 0 && out_w > 0, "%s: bad sizes", name);
+  plan_sweeps(p, (size_t)K * T * out_h * ((out_w + per_thread - 1) / per_thread), kBlock, kResizeMaxBlocks);
+  return DVIS_OK;
+}
+
 }  // namespace
+
+DVIS_EXPORT int dvis_postprocess_plan(int op, int K, int C, int cls_row_stride, int T, int img_h, int img_w, int out_h, int out_w,
+                                      int32_t *plan) {
+  DVIS_REQUIRE(plan, "postprocess_plan: null pointer");
+  PostPlan p;
+  int rc = DVIS_OK;
+  if (op == DVIS_POST_VPS_ARGMAX) rc = plan_vps(p, K, T, img_h, img_w, out_h, out_w);
+  else if (op == DVIS_POST_VSS_ARGMAX) rc = plan_vss(p, K, C, cls_row_stride, T, img_h, img_w, out_h, out_w);
+  else if (op == DVIS_POST_RESIZE2) rc = plan_resize2(p, "resize2", K, T, img_h, img_w, out_h, out_w, 1);
+  else if (op == DVIS_POST_RESIZE2_GT0) rc = plan_resize2(p, "resize2_gt0", K, T, img_h, img_w, out_h, out_w, 4);
+  else DVIS_REQUIRE(false, "postprocess_plan: op must be 0..3 (got %d)", op);
+  if (rc) return rc;
+  plan[0] = p.workgroups; plan[1] = p.sweeps; plan[2] = p.mfma; plan[3] = p.k4; plan[4] = p.identity2; plan[5] = p.lds_bytes;
+  return DVIS_OK;
+}
 
 DVIS_EXPORT int dvis_vps_argmax(const float *logits, int64_t stride_k, int64_t stride_t, const float *scores, int K, int T,
                                 int h, int w, int first_h, int first_w, int img_h, int img_w, int out_h, int out_w,
                                 int32_t *ids, uint8_t *conf, int32_t *areas, void *stream) {
-  DVIS_REQUIRE(K > 0 && K <= kMaxK && T >= 0 && h > 0 && w > 0 && first_h > 0 && first_w > 0 && img_h > 0 && img_w > 0 &&
-                   out_h > 0 && out_w > 0,
-               "vps_argmax: bad sizes (K must be 1..%d)", kMaxK);
+  PostPlan pl;
+  if (const int rc = plan_vps(pl, K, T, img_h, img_w, out_h, out_w)) return rc;
+  DVIS_REQUIRE(h > 0 && w > 0 && first_h > 0 && first_w > 0, "vps_argmax: bad sizes (K must be 1..%d)", kMaxK);
   DVIS_REQUIRE(img_h <= first_h && img_w <= first_w, "vps_argmax: image size exceeds the padded size");
-  DVIS_REQUIRE((size_t)T * out_h * out_w < 0x7fffffffu, "vps_argmax: more than 2^31 output pixels");
-  DVIS_REQUIRE(logits && scores && ids && conf && areas, "vps_argmax: null pointer");
+  DVIS_REQUIRE(scores && areas, "vps_argmax: null pointer");
   hipStream_t st = (hipStream_t)stream;
   if (const int rc = dvis_zero_words(areas, (size_t)3 * K, st, "vps_argmax: zero areas")) return rc;      // (a kernel, not a memset node)
-  if (T == 0) return DVIS_OK;
-  const size_t npix = (size_t)T * out_h * out_w;
-  size_t blocks = (npix + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;     // grid-stride: bounds the number of global area atomics
-  hipLaunchKernelGGL(vps_argmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, logits, stride_k, stride_t, scores, K, T,
+  if (pl.workgroups == 0) return DVIS_OK;       // T == 0: the maps are empty (their pointers may be null), the areas are zero
+  DVIS_REQUIRE(logits && ids && conf, "vps_argmax: null pointer");
+  hipLaunchKernelGGL(vps_argmax_kernel, dim3((unsigned)pl.workgroups), dim3(kBlock), 0, st, logits, stride_k, stride_t, scores, K, T,
                      h, w, first_h, first_w, img_h, img_w, out_h, out_w, ids, conf, areas);
   return dvis_check_launch("vps_argmax_kernel");
 }
@@ -329,36 +402,26 @@ DVIS_EXPORT int dvis_vps_argmax(const float *logits, int64_t stride_k, int64_t s
 DVIS_EXPORT int dvis_vss_argmax(const float *logits, int64_t stride_q, int64_t stride_t, const float *cls,
                                 int cls_row_stride, int Q, int C, int T, int h, int w, int first_h, int first_w, int img_h, int img_w, int out_h, int out_w,
                                 int64_t *out, void *stream) {
-  DVIS_REQUIRE(Q > 0 && C > 0 && C <= 128 && T >= 0 && h > 0 && w > 0 && first_h > 0 && first_w > 0 && img_h > 0 &&
-                   img_w > 0 && out_h > 0 && out_w > 0,
-               "vss_argmax: bad sizes (C must be 1..128)");
+  PostPlan pl;
+  if (const int rc = plan_vss(pl, Q, C, cls_row_stride, T, img_h, img_w, out_h, out_w)) return rc;
+  DVIS_REQUIRE(h > 0 && w > 0 && first_h > 0 && first_w > 0, "vss_argmax: bad sizes (C must be 1..%d)", kVssMaxC);
   DVIS_REQUIRE(img_h <= first_h && img_w <= first_w, "vss_argmax: image size exceeds the padded size");
+  if (pl.workgroups == 0) return DVIS_OK;       // T == 0: the map is empty (its pointer may be null)
   DVIS_REQUIRE(logits && cls && out, "vss_argmax: null pointer");
-  if (T == 0) return DVIS_OK;
-  DVIS_REQUIRE(cls_row_stride >= C && cls_row_stride % 32 == 0 && cls_row_stride <= 128 && (((uintptr_t)cls) & 15) == 0,
-               "vss_argmax: cls rows must be zero padded to a multiple of 32 floats (<= 128), 16-byte aligned");
-  const int k4 = cls_row_stride / 4;              // 8, 16, 24 or 32 float4 of class sums per thread
+  DVIS_REQUIRE((((uintptr_t)cls) & 15) == 0,
+               "vss_argmax: cls rows must be zero padded to a multiple of 32 floats (<= %d), 16-byte aligned", kVssMaxC);
   hipStream_t st = (hipStream_t)stream;
-  const size_t npix = (size_t)T * out_h * out_w;
-  size_t blocks = (npix + 255) / 256;
-  if (img_h == out_h && img_w == out_w && cls_row_stride == 128 && Q % 4 == 0) {
-    // GEMM form on the matrix cores (cls is padded to 128 columns; Q % 4 == 0 so that no row past the matrix is read)
-    const size_t lds = (size_t)Q * 132 * sizeof(float);
-    if (lds <= 64 * 1024) {
-      size_t nb = ((npix + 31) / 32 + 3) / 4;
-      if (nb > 256 * 9) nb = 256 * 9;
-      hipLaunchKernelGGL(vss_argmax_mfma_kernel, dim3((unsigned)nb), dim3(256), lds, st, logits, stride_q, stride_t, cls, Q, Q,
-                         C, T, h, w, first_h, first_w, out_h, out_w, out);
-      return dvis_check_launch("vss_argmax_mfma_kernel");
-    }
+  if (pl.mfma) {
+    hipLaunchKernelGGL(vss_argmax_mfma_kernel, dim3((unsigned)pl.workgroups), dim3(kBlock), (size_t)pl.lds_bytes, st, logits, stride_q,
+                       stride_t, cls, Q, Q, C, T, h, w, first_h, first_w, out_h, out_w, out);
+    return dvis_check_launch("vss_argmax_mfma_kernel");
   }
-  if (blocks > 256 * 16) blocks = 256 * 16;
-#define DVIS_VSS(K4_)                                                                                                   \
-  hipLaunchKernelGGL((vss_argmax_kernel<K4_>), dim3((unsigned)blocks), dim3(256), 0, st, logits, stride_q, stride_t, cls, \
+#define DVIS_VSS(K4_)                                                                                                          \
+  hipLaunchKernelGGL((vss_argmax_kernel<K4_>), dim3((unsigned)pl.workgroups), dim3(kBlock), 0, st, logits, stride_q, stride_t, cls, \
                      Q, C, T, h, w, first_h, first_w, img_h, img_w, out_h, out_w, out)
-  if (k4 == 8) DVIS_VSS(8);
-  else if (k4 == 16) DVIS_VSS(16);
-  else if (k4 == 24) DVIS_VSS(24);
+  if (pl.k4 == 8) DVIS_VSS(8);
+  else if (pl.k4 == 16) DVIS_VSS(16);
+  else if (pl.k4 == 24) DVIS_VSS(24);
   else DVIS_VSS(32);
 #undef DVIS_VSS
   return dvis_check_launch("vss_argmax_kernel");
@@ -367,17 +430,14 @@ DVIS_EXPORT int dvis_vss_argmax(const float *logits, int64_t stride_q, int64_t s
 DVIS_EXPORT int dvis_resize2_gt0(const float *logits, int64_t stride_k, int64_t stride_t, int K, int T, int h, int w,
                                  int first_h, int first_w, int img_h, int img_w, int out_h, int out_w, uint8_t *out,
                                  void *stream) {
-  DVIS_REQUIRE(K >= 0 && T >= 0 && h > 0 && w > 0 && first_h > 0 && first_w > 0 && img_h > 0 && img_w > 0 && out_h > 0 &&
-                   out_w > 0,
-               "resize2_gt0: bad sizes");
+  PostPlan pl;
+  if (const int rc = plan_resize2(pl, "resize2_gt0", K, T, img_h, img_w, out_h, out_w, 4)) return rc;
+  DVIS_REQUIRE(h > 0 && w > 0 && first_h > 0 && first_w > 0, "resize2_gt0: bad sizes");
   DVIS_REQUIRE(img_h <= first_h && img_w <= first_w, "resize2_gt0: image size exceeds the padded size");
-  if (K == 0 || T == 0) return DVIS_OK;
+  if (pl.workgroups == 0) return DVIS_OK;       // K == 0 or T == 0
   DVIS_REQUIRE(logits && out, "resize2_gt0: null pointer");
   DVIS_REQUIRE((((uintptr_t)out) & 3) == 0, "resize2_gt0: out must be 4-byte aligned");
-  const size_t ngroups = (size_t)K * T * out_h * ((out_w + 3) / 4);
-  size_t blocks = (ngroups + 255) / 256;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  hipLaunchKernelGGL(resize2_gt0_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, stride_k,
+  hipLaunchKernelGGL(resize2_gt0_kernel, dim3((unsigned)pl.workgroups), dim3(kBlock), 0, (hipStream_t)stream, logits, stride_k,
                      stride_t, K, T, h, w, first_h, first_w, img_h, img_w, out_h, out_w, out);
   return dvis_check_launch("resize2_gt0_kernel");
 }
@@ -385,20 +445,18 @@ DVIS_EXPORT int dvis_resize2_gt0(const float *logits, int64_t stride_k, int64_t 
 DVIS_EXPORT int dvis_resize2(const float *logits, int64_t stride_k, int64_t stride_t, int K, int T, int h, int w,
                              int first_h, int first_w, int img_h, int img_w, int out_h, int out_w, int sigmoid, float *out,
                              void *stream) {
-  DVIS_REQUIRE(K >= 0 && T >= 0 && h > 0 && w > 0 && first_h > 0 && first_w > 0 && img_h > 0 && img_w > 0 && out_h > 0 &&
-                   out_w > 0,
-               "resize2: bad sizes");
+  PostPlan pl;
+  if (const int rc = plan_resize2(pl, "resize2", K, T, img_h, img_w, out_h, out_w, 1)) return rc;
+  DVIS_REQUIRE(h > 0 && w > 0 && first_h > 0 && first_w > 0, "resize2: bad sizes");
   DVIS_REQUIRE(img_h <= first_h && img_w <= first_w, "resize2: image size exceeds the padded size");
-  if (K == 0 || T == 0) return DVIS_OK;
+  if (pl.workgroups == 0) return DVIS_OK;       // K == 0 or T == 0
   DVIS_REQUIRE(logits && out, "resize2: null pointer");
-  const size_t npix = (size_t)K * T * out_h * out_w;
-  size_t blocks = (npix + 255) / 256;
-  if (blocks > 256 * 64) blocks = 256 * 64;
   if (sigmoid)
-    hipLaunchKernelGGL(resize2_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, stride_k,
+    hipLaunchKernelGGL(resize2_kernel<true>, dim3((unsigned)pl.workgroups), dim3(kBlock), 0, (hipStream_t)stream, logits, stride_k,
                        stride_t, K, T, h, w, first_h, first_w, img_h, img_w, out_h, out_w, out);
   else
-    hipLaunchKernelGGL(resize2_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, stride_k,
+    hipLaunchKernelGGL(resize2_kernel<false>, dim3((unsigned)pl.workgroups), dim3(kBlock), 0, (hipStream_t)stream, logits, stride_k,
                        stride_t, K, T, h, w, first_h, first_w, img_h, img_w, out_h, out_w, out);
   return dvis_check_launch("resize2_kernel");
 }
+

@@ -18,7 +18,8 @@
 //        remaining channels       (scalar tail):   fma(w11, d, fma(w10, c, fma(w00, a, w01 * b)))
 //  sigmoid (aten/native/cpu/UnaryOpsKernel.cpp): 1 / (1 + exp(0 - x)) with
 //    vector lanes: Sleef_expf16_u10 (two-step Cody-Waite reduction, degree-5 polynomial, all FMA)
-//    scalar tail (the last n % 32 elements of each contiguous run): glibc expf (correctly rounded for our purposes)
+//    scalar tail (the last n % 32 elements of each contiguous run): glibc expf — NOT the correctly rounded exp: glibc_expf below follows its
+//                  own rounding (tests/test_postprocess_edges_gpu.py, saturation cases: 18 of 145800 floats were 1 ulp off before)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,11 +92,44 @@ __device__ __forceinline__ float sleef_expf(float d) {
   return u;
 }
 
+// glibc's expf (sysdeps/ieee754/flt-32/e_expf.c, the FMA build x86-64 hosts select): x * 32 / ln 2 = k + r in double, 2^(k / 32)
+// from a table, a cubic in r, one rounding to float.  Its error is below 0.502 ulp, not 0.5: about 1 result in 13000 is the
+// float NEXT to the correctly rounded one, and torch's scalar tail returns that one.  Checked on the host against libm's expf for
+// every float of |x| <= 105 (2.2e9 values, 0 differ; (float)exp((double)x) differs from it at 170648 of them).
+// tab[i] = bits(2^(i / 32)) - (i << 47), 2^(i / 32) correctly rounded.
+__device__ const unsigned long long kGlibcExp2fTab[32] = {
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull,
+    0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull,
+    0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull,
+    0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull, 0x3feea47eb03a5585ull,
+    0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull,
+    0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+
+__device__ __forceinline__ float glibc_expf(float x) {
+#pragma clang fp contract(off)
+  if (x > 0x1.62e42ep6f) return INFINITY;          // its overflow and underflow cut-offs; between them the double carries the range
+  if (x < -0x1.9fe368p6f) return 0.f;
+  const double InvLn2N = 0x1.71547652b82fep+5, Shift = 0x1.8p52;
+  const double C0 = 0x1.c6af84b912394p-5 / 32768, C1 = 0x1.ebfce50fac4f3p-3 / 1024, C2 = 0x1.62e42ff0c52d6p-1 / 32;
+  const double xd = (double)x;
+  double kd = InvLn2N * xd + Shift;                // round to nearest: k in the low bits
+  const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
+  kd -= Shift;
+  const double r = __builtin_fma(InvLn2N, xd, -kd);
+  const double s = __longlong_as_double((long long)(kGlibcExp2fTab[ki & 31] + (ki << 47)));      // 2^(k / 32)
+  const double z = __builtin_fma(C0, r, C1);
+  double y = __builtin_fma(C2, r, 1.0);
+  y = __builtin_fma(z, r * r, y);
+  return (float)(y * s);                           // denormal results round here, as in glibc
+}
+
 // torch.sigmoid on a float CPU tensor; `scalar_tail`: the element sits in the last n % 32 of its contiguous run
 __device__ __forceinline__ float sigmoid(float x, bool scalar_tail) {
 #pragma clang fp contract(off)
   const float nx = 0.f - x;
-  const float e = scalar_tail ? (float)exp((double)nx) : sleef_expf(nx);
+  const float e = scalar_tail ? glibc_expf(nx) : sleef_expf(nx);
   return 1.f / (1.f + e);
 }
 

@@ -1064,6 +1064,37 @@ def ov_ensemble(in_logits, out_logits, overlapping, alpha, beta, valid=None):
     return out
 
 
+POSTPROCESS_OPS = ("vps_argmax", "vss_argmax", "resize2", "resize2_gt0")                   # DVIS_POST_* of dvis_hip.h
+PostprocessPlan = collections.namedtuple("PostprocessPlan", "workgroups sweeps form K4 identity lds_bytes row_stride")
+
+
+def vss_row_stride(C):
+    """Floats per row of the zero-padded class matrix that ``vss_argmax`` hands to dvis_vss_argmax: C rounded up to 32."""
+    return (int(C) + 31) // 32 * 32
+
+
+def postprocess_plan(op, K, T, img_size, out_hw, C=None):
+    """How csrc/postprocess.hip would run ``vps_argmax`` / ``vss_argmax`` / ``resize2`` / ``resize2_gt0`` (`op`, one of
+    POSTPROCESS_OPS) on K candidate maps (vss_argmax: K queries and C classes) of T frames, without launching it:
+    PostprocessPlan(workgroups, sweeps, form, K4, identity, lds_bytes, row_stride) — the workgroups launched and the grid-stride
+    sweeps they make (0, 0: nothing is launched); for vss_argmax also the form ("mfma" or "generic"), K4 (float4 of class sums per
+    thread: the generic form's instance), whether the second resize is the identity, the dynamic LDS bytes and the class matrix's row
+    stride (``vss_row_stride``); None / 0 / False for the other ops.  The answer comes from dvis_postprocess_plan, the function the
+    launches themselves consult; only sizes are read, so no GPU is needed.  A size the call refuses raises with the call's message."""
+    code = POSTPROCESS_OPS.index(op)
+    vss = op == "vss_argmax"
+    if vss == (C is None):
+        raise RuntimeError("postprocess_plan: C is the class count of vss_argmax (and of nothing else)")
+    stride = vss_row_stride(C) if vss else 0
+    plan = (ctypes.c_int32 * 6)()
+    rc = native.lib().dvis_postprocess_plan(code, int(K), int(C) if vss else 0, stride, int(T), int(img_size[0]), int(img_size[1]),
+                                            int(out_hw[0]), int(out_hw[1]), plan)
+    native.check(rc, "dvis_postprocess_plan")
+    if not vss:
+        return PostprocessPlan(plan[0], plan[1], None, 0, False, 0, 0)
+    return PostprocessPlan(plan[0], plan[1], "mfma" if plan[2] else "generic", plan[3], bool(plan[4]), plan[5], stride)
+
+
 def vps_argmax(mask_logits_kthw, scores, first_resize_size, img_size, out_hw):
     """Fused panoptic arg-max (see dvis_vps_argmax).  mask_logits_kthw: float32 GPU (K, T, h, w) view whose last two
     dims are contiguous; scores float32 (K,).  Returns ids int32 (T,H,W), conf bool (T,H,W), areas int32 (3, K)."""
@@ -1131,7 +1162,7 @@ def vss_argmax(mask_logits_qthw, mask_cls, first_resize_size, img_size, out_hw):
     if not m.is_cuda or m.dtype != torch.float32 or m.stride(3) != 1 or m.stride(2) != w:
         raise RuntimeError("vss_argmax: logits must be a float32 GPU (Q, T, h, w) view with contiguous (h, w) maps")
     C = mask_cls.shape[1]
-    Cp = (C + 31) // 32 * 32
+    Cp = vss_row_stride(C)
     cls = torch.nn.functional.pad(mask_cls.to(torch.float32), (0, Cp - C)).contiguous()     # zero columns: never the max
     oh, ow = int(out_hw[0]), int(out_hw[1])
     out = torch.empty((T, oh, ow), dtype=torch.int64, device=m.device)

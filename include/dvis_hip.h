@@ -530,7 +530,8 @@ int dvis_adapter_res2(const float *g, const float *c1, const float *x1, const fl
  *   ids = argmax_k scores[k] * prob_k (first maximum wins), conf = prob_ids >= 0.5,
  *   areas (3, K) int32 = [ (ids == k).sum(), (prob_k >= 0.5).sum(), ((ids == k) & conf).sum() ]   (zeroed inside).
  *   logits: K x T maps of h*w floats, logits[k][t] at logits + k*stride_k + t*stride_t; 1 <= K <= 256.
- *   ids (T, out_h, out_w) int32, conf (T, out_h, out_w) uint8.
+ *   ids (T, out_h, out_w) int32, conf (T, out_h, out_w) uint8.  T == 0: logits, ids and conf are empty and may be null; the
+ *   areas are still zeroed.
  */
 int dvis_vps_argmax(const float *logits, int64_t stride_k, int64_t stride_t, const float *scores, int K, int T,
                     int h, int w, int first_h, int first_w, int img_h, int img_w, int out_h, int out_w,
@@ -563,6 +564,33 @@ int dvis_resize2(const float *logits, int64_t stride_k, int64_t stride_t, int K,
 int dvis_vss_argmax(const float *logits, int64_t stride_q, int64_t stride_t, const float *cls, int cls_row_stride, int Q,
                     int C, int T, int h, int w, int first_h, int first_w, int img_h, int img_w, int out_h, int out_w,
                     int64_t *out, void *stream);
+
+/*
+ * HOST function: how the four entry points above would run a problem, without launching anything (no GPU needed; only sizes are
+ * read).  The launches take their grid and their dispatch from the same function, so the answer is what runs.
+ *   op: DVIS_POST_*;  K: the candidates (Q for DVIS_POST_VSS_ARGMAX);  C, cls_row_stride: DVIS_POST_VSS_ARGMAX only, as in the call;
+ *   T, img_h, img_w, out_h, out_w: as in the call (the stride-4 and padded sizes decide nothing here).
+ *   plan[0] = workgroups launched (256 threads each);  0 when the call launches nothing (T == 0, or K == 0 of the resizes)
+ *   plan[1] = grid-stride sweeps = ceil(work items / (workgroups * items per workgroup and sweep)).  A work item is one output pixel
+ *             (T out_h out_w of them; vps_argmax and the generic vss_argmax: at most 256 * 16 workgroups of 256), one float
+ *             (K T out_h out_w; resize2: at most 256 * 64 of 256), one group of 4 pixels of a row (K T out_h ceil(out_w / 4);
+ *             resize2_gt0: at most 256 * 64 of 256) or one 32-pixel wave chunk (ceil(T out_h out_w / 32); the MFMA vss_argmax:
+ *             at most 256 * 9 workgroups of 4)
+ *   DVIS_POST_VSS_ARGMAX only, 0 otherwise:
+ *   plan[2] = 1: the MFMA form (cls_row_stride == 128, Q % 4 == 0, img == out and Q * 132 * 4 bytes <= 64 KB of LDS, that is
+ *             Q <= 124), 0: the generic one-pixel-per-thread form
+ *   plan[3] = K4 = cls_row_stride / 4 (8, 16, 24 or 32): the float4 of class sums a thread of the generic form holds, its instance
+ *   plan[4] = 1: img == out, the second resize is the identity (the generic form's prefetching branch; required by the MFMA form)
+ *   plan[5] = dynamic LDS bytes of the launch (Q * 132 * 4 on the MFMA form, else 0)
+ * The size checks of the call itself apply and refuse with the call's message (K must be 1..256; C must be 1..128; the row stride).
+ */
+enum {
+  DVIS_POST_VPS_ARGMAX = 0,
+  DVIS_POST_VSS_ARGMAX = 1,
+  DVIS_POST_RESIZE2 = 2,
+  DVIS_POST_RESIZE2_GT0 = 3
+};
+int dvis_postprocess_plan(int op, int K, int C, int cls_row_stride, int T, int img_h, int img_w, int out_h, int out_w, int32_t *plan);
 
 /*
  * HOST function: minimum-cost assignment of an nr x nc (nr <= nc) row-major double cost matrix,

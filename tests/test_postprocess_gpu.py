@@ -16,6 +16,7 @@ import torch.nn.functional as F
 
 import intcmp
 from conftest import Golden
+from postprocess_cases import _cpu_sequence, _logits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -30,18 +31,6 @@ CASES = [
     (4, 2, (46, 80), (184, 320), (180, 300), (360, 600)),    # generic both, crop in x with a 12-column tail
     (5, 4, (23, 40), (92, 160), (90, 160), (45, 80)),        # down-size second stage, small kernel
 ]
-
-
-def _logits(K, T, hw, seed):
-    g = torch.Generator().manual_seed(seed)
-    return (torch.randn(T, K, *hw, generator=g) * 3).permute(1, 0, 2, 3)      # (K,T,h,w) strided like mask_fn's output
-
-
-def _cpu_sequence(logits, first, img, out, sigmoid):
-    m = F.interpolate(logits.contiguous(), size=first, mode="bilinear", align_corners=False)[:, :, :img[0], :img[1]]
-    if sigmoid:
-        m = m.sigmoid()
-    return F.interpolate(m, size=out, mode="bilinear", align_corners=False)
 
 
 @pytest.mark.parametrize("sigmoid", [False, True])
