@@ -361,6 +361,31 @@ def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale
     return out
 
 
+# --- first half of a ConvNeXt block (csrc/dwconv_ln.hip) ---------------------------------------------------------------------------
+def dwconv7x7_ln_tokens(x, conv_dw, norm, hw=None):
+    """functions.dwconv7x7_ln_tokens as torch ops on x's device and in its dtype: the token-major map x (B, h, w, C) (or (B, h w, C)
+    with hw = (h, w)) goes to NCHW, through the depthwise convolution, back to NHWC and through the LayerNorm over C — timm's
+    ConvNeXtBlock up to mlp.fc1 -> a tensor of x's shape."""
+    B = x.shape[0]
+    h, w = (x.shape[1], x.shape[2]) if hw is None else (int(hw[0]), int(hw[1]))
+    C = x.shape[-1]
+    z = F.conv2d(x.reshape(B, h, w, C).permute(0, 3, 1, 2), conv_dw.weight.to(x.dtype),
+                 None if conv_dw.bias is None else conv_dw.bias.to(x.dtype), stride=1, padding=3, groups=C)
+    y = F.layer_norm(z.permute(0, 2, 3, 1), (C,), norm.weight.to(x.dtype), norm.bias.to(x.dtype), norm.eps)
+    return y.reshape(x.shape)
+
+
+def causal_self_attention(qkv, heads, attn_mask):
+    """The self-attention of CLIP's text tower as plain torch ops, on any device: qkv (N, L, 3 D) = the block's in-projection, columns
+    [3][heads][d]; attn_mask (L, L) additive (-inf above the diagonal) -> (N, L, D), ready for the out-projection.  This is NOT a hot
+    path: the tower runs once per vocabulary on 77 tokens and the meta-architecture caches its result, so there is no kernel for it."""
+    N, L, D3 = qkv.shape
+    d = D3 // 3 // heads
+    q, k, v = qkv.view(N, L, 3, heads, d).permute(2, 0, 3, 1, 4)
+    a = torch.softmax((q * d ** -0.5) @ k.transpose(-1, -2) + attn_mask.to(qkv.dtype), dim=-1)
+    return (a @ v).permute(0, 2, 1, 3).reshape(N, L, heads * d)
+
+
 # --- classification of the open-vocabulary (FC-CLIP) heads (csrc/mask_pool.hip, csrc/ov_class_logits.hip) ---------------------------
 def mask_pool(x, mask_logits):
     """functions.mask_pool as torch ops: x (B, C, H, W), mask_logits (B, Q, H, W) (any strides) -> (sum (B, Q, C) of x over the pixels

@@ -73,15 +73,15 @@ def configurable(init_func):
 
 def _populate():
     """Import the modules whose classes register themselves (idempotent)."""
-    from . import backbone, meta_architecture, pixel_decoder, swin, transformer_decoder, vit_adapter  # noqa: F401
+    from . import backbone, convnext, meta_architecture, pixel_decoder, swin, transformer_decoder, vit_adapter  # noqa: F401
 
 
 # ---- the builders the reference's from_config functions call ------------------------------------------------------
 def build_backbone(cfg, input_shape=None):
     """detectron2.modeling.build_backbone: ``BACKBONE_REGISTRY.get(cfg.MODEL.BACKBONE.NAME)(cfg, input_shape)``.
     Names served here: ``build_resnet_backbone`` (R50, the fused inference ResNet of backbone.py),
-    ``D2VitAdapterDinoV2`` (vit_adapter.py) and ``D2SwinTransformer`` (swin.py: inference, and frozen under the tracker / refiner
-    stages); anything else is detectron2's to build when it is importable."""
+    ``D2VitAdapterDinoV2`` (vit_adapter.py), ``D2SwinTransformer`` (swin.py: inference, and frozen under the tracker / refiner
+    stages) and ``CLIP`` (convnext.py: the frozen CLIP ConvNeXt of the open-vocabulary family); anything else is detectron2's to build when it is importable."""
     _populate()
     name = cfg.MODEL.BACKBONE.NAME
     if name in BACKBONE_REGISTRY:

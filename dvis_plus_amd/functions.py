@@ -915,6 +915,71 @@ def window_attention(qkv, qkv_bias, bias_table, B, H, W, heads, ws, shift, scale
     return out
 
 
+# ---- first half of a ConvNeXt block: csrc/dwconv_ln.hip ---------------------------------------------------------------------------
+def _dwconv7x7_ln_shape(x, hw):
+    """(B, h, w, C) of the token-major map: x (B, h, w, C), or x (B, h w, C) with hw = (h, w)."""
+    if x.dim() == 4 and hw is None:
+        return tuple(x.shape)
+    if x.dim() == 3 and hw is not None and int(hw[0]) * int(hw[1]) == x.shape[1]:
+        return x.shape[0], int(hw[0]), int(hw[1]), x.shape[2]
+    raise RuntimeError(f"dwconv7x7_ln_tokens: expected x (B, h, w, C), or x (B, h w, C) with hw=(h, w); got {tuple(x.shape)} and hw={hw}")
+
+
+def dwconv7x7_ln_tokens_ok(x, conv_dw, norm, hw=None):
+    """Whether ``dwconv7x7_ln_tokens`` runs csrc/dwconv_ln.hip on these operands: float32 GPU tensors on one device, a depthwise
+    7 x 7 / stride 1 / padding 3 convolution, an affine LayerNorm over C, and a width the library serves (asked of the library
+    itself: C % 4 == 0, 8 <= C <= 1536) with one frame below 2^31 bytes."""
+    B, h, w, C = _dwconv7x7_ln_shape(x, hw)
+    tensors = [x, conv_dw.weight, conv_dw.bias, norm.weight, norm.bias]
+    return (all(t is None or (t.is_cuda and t.device == x.device and t.dtype == torch.float32) for t in tensors)
+            and norm.weight is not None and norm.bias is not None and tuple(conv_dw.weight.shape) == (C, 1, 7, 7)
+            and tuple(norm.weight.shape) == (C,) and tuple(conv_dw.stride) == (1, 1) and tuple(conv_dw.padding) == (3, 3)
+            and tuple(conv_dw.dilation) == (1, 1) and conv_dw.groups == C and h * w * C * 4 < 2 ** 31
+            and bool(native.lib().dvis_dwconv7x7_ln_tokens_supported(int(C))))
+
+
+def dwconv7x7_ln_tokens(x, conv_dw, norm, hw=None, out=None):
+    """``norm(conv_dw(x_nchw).permute(0, 2, 3, 1))`` of a ConvNeXt block — depthwise 7 x 7 convolution + bias, then LayerNorm over the
+    channels — on the TOKEN-major map, in one kernel (csrc/dwconv_ln.hip; contract: dvis_dwconv7x7_ln_tokens in include/dvis_hip.h).
+    x (B, h, w, C), or (B, h w, C) with hw = (h, w); a view whose frames are contiguous (h w C) blocks at a batch stride that is a
+    multiple of 4 floats is read in place.  conv_dw: an ``nn.Conv2d(C, C, 7, padding=3, groups=C)`` (bias optional); norm: an affine
+    ``nn.LayerNorm(C)``.  -> a new contiguous tensor of x's shape (or `out`, a contiguous float32 GPU tensor of that shape that does
+    not overlap x: every element of it is written).
+    Exact fp32, a fixed operation order: the same bits every call, and a frame's bits do not depend on B.  Operands the kernel does
+    not serve (``dwconv7x7_ln_tokens_ok``) raise (DVIS_STRICT=0: cpu_ops.dwconv7x7_ln_tokens' torch formulation on the GPU).  CPU
+    tensors (any float dtype) take cpu_ops.dwconv7x7_ln_tokens.  No backward on the GPU: the trunk is frozen in every config."""
+    B, h, w, C = _dwconv7x7_ln_shape(x, hw)
+    tensors = [x, conv_dw.weight, conv_dw.bias, norm.weight, norm.bias]
+    if _on_cpu(*[t for t in tensors if t is not None]):
+        return cpu_ops.dwconv7x7_ln_tokens(x, conv_dw, norm, hw)
+    _no_backward("dwconv7x7_ln_tokens", tensors)
+    if not dwconv7x7_ln_tokens_ok(x, conv_dw, norm, hw):
+        _torch_path("dwconv7x7_ln_tokens", x, f"needs float32 tensors on one GPU, a depthwise 7 x 7 / stride 1 / padding 3 convolution "
+                    f"and an affine LayerNorm over C % 4 == 0, 8 <= C <= 1536, one frame below 2^31 bytes (C={C}, frame h w C * 4 = "
+                    f"{h * w * C * 4} bytes)")
+        return cpu_ops.dwconv7x7_ln_tokens(x, conv_dw, norm, hw)
+    frame = h * w * C
+    xs = x.detach()
+    in_place = xs.data_ptr() % 16 == 0 and (B == 0 or (xs[0].is_contiguous()
+                                                       and (B == 1 or (xs.stride(0) % 4 == 0 and xs.stride(0) >= frame))))
+    if not in_place:
+        xs = xs.contiguous()
+    bstride = xs.stride(0) if B > 1 else frame
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    elif out.shape != x.shape or out.dtype != torch.float32 or out.device != x.device:
+        raise RuntimeError(f"dwconv7x7_ln_tokens: out must be float32 {tuple(x.shape)} on x's GPU")
+    wt = conv_dw.weight.detach().contiguous()
+    bias = None if conv_dw.bias is None else native.dev_ptr(conv_dw.bias.detach().contiguous(), "bias")
+    with torch.cuda.device(x.device):
+        rc = native.lib().dvis_dwconv7x7_ln_tokens(ctypes.c_void_p(xs.data_ptr()), native.dev_ptr(out, "out"), bstride, B, h, w, C,
+                                                   native.dev_ptr(wt, "weight"), bias, native.dev_ptr(norm.weight.detach(), "gamma"),
+                                                   native.dev_ptr(norm.bias.detach(), "beta"), float(norm.eps),
+                                                   native.stream_ptr(x.device))
+    native.check(rc, "dvis_dwconv7x7_ln_tokens")
+    return out
+
+
 # ---- classification of the open-vocabulary (FC-CLIP) heads: csrc/mask_pool.hip, csrc/ov_class_logits.hip ----------------------------
 MaskPoolPlan = collections.namedtuple("MaskPoolPlan", "slab slabs")
 
@@ -1216,6 +1281,14 @@ def add_layer_norm(x, res, norm, pos=None):
                 ctypes.c_void_p(out_pos.data_ptr()), rows, C, float(norm.eps), native.stream_ptr(x.device))
     native.check(rc, "dvis_add_layernorm")
     return out if pos is None else (out, out_pos)
+
+
+def layer_norm(x, norm):
+    """``norm(x)`` for an ``nn.LayerNorm`` over the last dim: the fused kernel where it serves the width (C <= 1024, C % 4 == 0),
+    torch's LayerNorm beyond (the 1536 / 3072-wide norms of Swin-L and of the large CLIP ConvNeXt's head)."""
+    if x.shape[-1] <= 1024 and x.shape[-1] % 4 == 0:
+        return add_layer_norm(x.contiguous(), None, norm)
+    return norm(x)
 
 
 def bias_relu_maxpool(x, bias=None):

@@ -177,6 +177,8 @@ SIGNATURES = {
     "dvis_mask_pool": (_i, [_p, _p, _i64, _i64, _i, _i, _i, _i64, _p, _p, _p, _p]),
     "dvis_text_class_logits": (_i, [_p, _i64, _p, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
     "dvis_ov_ensemble": (_i, [_p, _p, _p, _p, _f, _f, _i, _i, _p, _p]),
+    "dvis_dwconv7x7_ln_tokens_supported": (_i, [_i]),
+    "dvis_dwconv7x7_ln_tokens": (_i, [_p, _p, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _f, _p]),
 }
 
 _lib = None

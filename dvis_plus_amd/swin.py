@@ -27,11 +27,21 @@ from .registry import BACKBONE_REGISTRY, ShapeSpec
 
 
 def _layer_norm(x, norm):
-    """``norm(x)``: the fused kernel where it serves the width (C <= 1024: every norm of Swin-T / S / B and all but the last
+    """``Fn.layer_norm``: the fused kernel where it serves the width (C <= 1024: every norm of Swin-T / S / B and all but the last
     stage's of Swin-L), torch's LayerNorm beyond (Swin-L's 1536-wide last stage and its 1536 / 3072-wide merging norms)."""
-    if x.shape[-1] <= 1024 and x.shape[-1] % 4 == 0:
-        return Fn.add_layer_norm(x.contiguous(), None, norm)
-    return norm(x)
+    return Fn.layer_norm(x, norm)
+
+
+def patch_tokens(x, proj, norm=None):
+    """A stride-p p x p convolution `proj` over (B, Cin, H, W), H and W multiples of p, as a linear layer over flattened patches
+    — one gather into (B h w, Cin p p) rows and a GEMM whose output already is the token matrix —, then `norm`:
+    -> tokens (B, h w, C), h, w.  Shared by PatchEmbed and the CLIP ConvNeXt stem."""
+    ph, pw = proj.kernel_size
+    B, Cin, H, W = x.shape
+    h, w = H // ph, W // pw
+    rows = x.reshape(B, Cin, h, ph, w, pw).permute(0, 2, 4, 1, 3, 5).reshape(B * h * w, Cin * ph * pw)
+    t = Fn.linear(rows, proj.weight.view(proj.out_channels, -1), proj.bias, tall=True).view(B, h * w, proj.out_channels)
+    return (t if norm is None else Fn.layer_norm(t, norm)), h, w
 
 
 class Mlp(nn.Module):
@@ -146,12 +156,7 @@ class PatchEmbed(nn.Module):
             x = F.pad(x, (0, pw - W % pw))
         if H % ph != 0:
             x = F.pad(x, (0, 0, 0, ph - H % ph))
-        h, w = x.shape[2] // ph, x.shape[3] // pw
-        rows = x.reshape(B, Cin, h, ph, w, pw).permute(0, 2, 4, 1, 3, 5).reshape(B * h * w, Cin * ph * pw)
-        t = Fn.linear(rows, self.proj.weight.view(self.embed_dim, -1), self.proj.bias, tall=True).view(B, h * w, self.embed_dim)
-        if self.norm is not None:
-            t = _layer_norm(t, self.norm)
-        return t, h, w
+        return patch_tokens(x, self.proj, self.norm)
 
 
 class SwinTransformer(nn.Module):

@@ -1082,6 +1082,25 @@ int dvis_text_class_logits(const float *x, int64_t x_stride, const float *dots, 
 int dvis_ov_ensemble(const float *in_logits, const float *out_logits, const float *overlapping, const int32_t *valid, float alpha,
                      float beta, int R, int K, float *out, void *stream);
 
+/*
+ * First half of a ConvNeXt block on a TOKEN-major map (csrc/dwconv_ln.hip): depthwise 7 x 7 convolution (padding 3) + bias, then
+ * LayerNorm over the channels — conv_dw, the permute to NHWC and norm of timm's ConvNeXtBlock, up to the input of mlp.fc1.
+ *   x: token (b, y, x) at x + b * batch_stride + (y * w + x) * C (the layout convention of dvis_dwconv3x3_tokens); out (B h w, C)
+ *   contiguous rows, not overlapping x; weight (C, 1, 7, 7) = C x 49; bias (C) or null; gamma, beta (C).
+ *   z[c] = bias[c] + sum_ky sum_kx weight[c, ky, kx] * x[b, y + ky - 3, x + kx - 3, c]   (zeros outside the map)
+ *   out  = (z - mean_c z) / sqrt(var_c z + eps) * gamma + beta                           (biased variance)
+ * Exact fp32.  The 49 taps of an output are one fma chain, ky outer and kx inner, a padding tap contributing a zero (not a skipped
+ * step); the mean is reduced first, then the sum of squared deviations from it, both from the z values held in registers, with a
+ * cross-lane shape that depends on C alone: an output's bits do not depend on its position in a tile, on B or on its batch mates.
+ * No atomics, no workspace, no memset, no host synchronisation: capturable; every output element is written; the same bits every call.
+ * Served: C % 4 == 0, 8 <= C <= 1536, any h, w >= 1, one frame (h w C floats) below 2^31 bytes, 16-byte aligned pointers,
+ * batch_stride % 4 == 0 and >= h w C.  Everything else is refused before the launch, naming the value.
+ * dvis_dwconv7x7_ln_tokens_supported: 1 where C is served.
+ */
+int dvis_dwconv7x7_ln_tokens_supported(int C);
+int dvis_dwconv7x7_ln_tokens(const float *x, float *out, int64_t batch_stride, int B, int h, int w, int C, const float *weight,
+                             const float *bias, const float *gamma, const float *beta, float eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
