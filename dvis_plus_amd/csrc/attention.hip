@@ -1031,12 +1031,10 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float *__restri
 }  // namespace
 
 DVIS_EXPORT int64_t dvis_attention_ws_bytes_k(int BH, int Lq, int Lk, int d, int kernel) {
-  if (kernel != 2) return dvis_attention_ws_bytes(BH, Lq, Lk, d);
-  if (BH <= 0 || Lq <= 0 || Lk <= 0 || d != 64) return 0;
-  return (int64_t)BH * ((int64_t)Lq + 2 * (int64_t)Lk) * 128 * (int64_t)sizeof(_Float16);       // the two-term f16 images of Q, K, V
-}
-
-DVIS_EXPORT int64_t dvis_attention_ws_bytes(int BH, int Lq, int Lk, int d) {
+  if (kernel == 2) {
+    if (BH <= 0 || Lq <= 0 || Lk <= 0 || d != 64) return 0;
+    return (int64_t)BH * ((int64_t)Lq + 2 * (int64_t)Lk) * 128 * (int64_t)sizeof(_Float16);     // the two-term f16 images of Q, K, V
+  }
   if (BH <= 0 || Lq <= 0 || Lk <= 0 || d <= 0) return 0;
   const SplitPlan p = plan_split(Lq, Lk);
   int ns = p.nsplit;
@@ -1121,7 +1119,7 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
   }
   if (plan.served_by == DVIS_ATTN_KEYSPLIT) {
     const AttnPlan &kp = plan;
-    DVIS_REQUIRE(kp.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes)");
+    DVIS_REQUIRE(kp.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes_k)");
     float *kws_o = (float *)ws;
     float *kws_ml = kws_o ? kws_o + (size_t)BH * kp.nsplit * Lq * d : nullptr;
     const long long units = (long long)BH * kp.qchunks * kp.nsplit;
@@ -1152,7 +1150,7 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
     return dvis_check_launch("attn_short_kernel");
   }
   const AttnPlan &p = plan;      // DVIS_ATTN_FWD
-  DVIS_REQUIRE(p.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes)");
+  DVIS_REQUIRE(p.nsplit == 1 || ws, "attention: workspace required (dvis_attention_ws_bytes_k)");
   float *ws_o = (float *)ws;
   float *ws_ml = ws_o ? ws_o + (size_t)BH * p.nsplit * Lq * d : nullptr;
   const dim3 grid(p.nsplit, BH, p.qchunks), block(512);
@@ -1168,14 +1166,6 @@ static int attention_launch(const float *q, const int64_t *q_strides, const floa
   hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, ws_o, ws_ml, p.nsplit,
                      Lq, d, heads, total, out, os);
   return dvis_check_launch("attn_combine_kernel");
-}
-
-DVIS_EXPORT int dvis_attention_forward(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
-                                       const float *v, const int64_t *v_strides, float *out, const int64_t *o_strides,
-                                       const uint8_t *mask, const int32_t *allowed_count, int B, int heads, int Lq,
-                                       int Lk, int d, float scale, void *ws, void *stream) {
-  return attention_launch(q, q_strides, k, k_strides, v, v_strides, out, o_strides, mask, allowed_count, B, heads, Lq, Lk, d,
-                          scale, ws, stream, 0);
 }
 
 // Kernel 2's second launch alone: Q, K, V are already in `ws` as two-term f16 images (written by dvis_x3_tile_linear_qkv, the qkv

@@ -503,14 +503,8 @@ static int nchw_to_tokens_launch(const float *x, float *out, int64_t N, int C, i
   return dvis_check_launch("nchw_to_tokens_kernel");
 }
 
-DVIS_EXPORT int dvis_nchw_to_tokens(const float *x, float *out, int64_t N, int C, int64_t HW, int64_t S, int64_t row0,
-                                    void *stream) {
-  return nchw_to_tokens_launch(x, out, N, C, HW, S, row0, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-DVIS_EXPORT int dvis_nchw_to_tokens_affine(const float *x, const float *scale, const float *shift, const float *pos,
-                                           float *out, float *out_pos, int64_t N, int C, int64_t HW, int64_t S,
-                                           int64_t row0, void *stream) {
+DVIS_EXPORT int dvis_nchw_to_tokens(const float *x, const float *scale, const float *shift, const float *pos, float *out,
+                                    float *out_pos, int64_t N, int C, int64_t HW, int64_t S, int64_t row0, void *stream) {
   return nchw_to_tokens_launch(x, out, N, C, HW, S, row0, scale, shift, pos, out_pos, stream);
 }
 
@@ -543,7 +537,8 @@ static int add_layernorm_launch(const float *x, const float *res, int64_t res_ro
   DVIS_REQUIRE(x && gamma && beta && out, "add_layernorm: null pointer");
   DVIS_REQUIRE(C % 4 == 0 && C <= 1024, "add_layernorm: C must be a multiple of 4 and <= 1024 (got %d)", C);
   DVIS_REQUIRE(res == nullptr || res_row_stride % 4 == 0, "add_layernorm: residual row stride must be a multiple of 4");
-  DVIS_REQUIRE(pos == nullptr || (pos_rows > 0 && out_pos != nullptr), "add_layernorm: pos needs pos_rows > 0 and out_pos");
+  DVIS_REQUIRE((pos == nullptr) == (out_pos == nullptr) && (pos == nullptr || pos_rows > 0),
+               "add_layernorm: pos and out_pos are given together, and then pos_rows > 0");
   const uintptr_t al = (uintptr_t)x | (uintptr_t)res | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out |
                        (uintptr_t)pos | (uintptr_t)out_pos;
   DVIS_REQUIRE((al & 15) == 0, "add_layernorm: pointers must be 16-byte aligned");
@@ -560,14 +555,8 @@ static int add_layernorm_launch(const float *x, const float *res, int64_t res_ro
 }
 
 DVIS_EXPORT int dvis_add_layernorm(const float *x, const float *res, int64_t res_row_stride, const float *gamma,
-                                   const float *beta, float *out, int64_t rows, int C, float eps, void *stream) {
-  return add_layernorm_launch(x, res, res_row_stride, gamma, beta, out, rows, C, eps, nullptr, 0, nullptr, stream);
-}
-
-DVIS_EXPORT int dvis_add_layernorm_pos(const float *x, const float *res, int64_t res_row_stride, const float *gamma,
-                                       const float *beta, float *out, const float *pos, int64_t pos_rows, float *out_pos,
-                                       int64_t rows, int C, float eps, void *stream) {
-  DVIS_REQUIRE(pos && out_pos, "add_layernorm_pos: null pos / out_pos");
+                                   const float *beta, float *out, const float *pos, int64_t pos_rows, float *out_pos,
+                                   int64_t rows, int C, float eps, void *stream) {
   return add_layernorm_launch(x, res, res_row_stride, gamma, beta, out, rows, C, eps, pos, pos_rows, out_pos, stream);
 }
 
@@ -628,15 +617,8 @@ DVIS_EXPORT int dvis_adapter_res2(const float *g, const float *c1, const float *
   return dvis_check_launch("adapter_res2_kernel");
 }
 
-DVIS_EXPORT int dvis_upsample_add(const float *lateral, const float *top, float *out, int64_t planes, int H, int W, int h,
-                                  int w, void *stream) {
-  return upsample_add_launch(lateral, top, out, planes, H, W, h, w, nullptr, nullptr, stream);
-}
-
-DVIS_EXPORT int dvis_upsample_add_affine(const float *lateral, const float *lat_scale, const float *lat_shift,
-                                         const float *top, float *out, int64_t planes, int H, int W, int h, int w,
-                                         void *stream) {
-  DVIS_REQUIRE(lat_scale && lat_shift, "upsample_add_affine: null scale / shift");
+DVIS_EXPORT int dvis_upsample_add(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top,
+                                  float *out, int64_t planes, int H, int W, int h, int w, void *stream) {
   return upsample_add_launch(lateral, top, out, planes, H, W, h, w, lat_scale, lat_shift, stream);
 }
 

@@ -532,25 +532,16 @@ DVIS_EXPORT int64_t dvis_x3_tile_packed_bytes(int N, int K) {
   return (int64_t)N * K * 4;
 }
 
-DVIS_EXPORT int dvis_x3_tile_pack(const float *w, int64_t ldw, int N, int K, int wexp, void *packed, void *stream) {
+// The weight image, with the k slots of every k-tile in the order a row image's producer writes them (x3_tile_k): 0 natural (the
+// stand-alone and LayerNorm producers), 1 the GELU form of dvis_x3_tile_linear_image, 2 dvis_attention_x3_packed_image (K = heads * 64).
+DVIS_EXPORT int dvis_x3_tile_pack(const float *w, int64_t ldw, int N, int K, int wexp, int order, void *packed, void *stream) {
   DVIS_REQUIRE(dvis_x3_tile_supported(N, K), "dvis_x3_tile_pack: N %% 256 == 0 and K %% 32 == 0 are required (N %d, K %d)", N, K);
   DVIS_REQUIRE(w && packed && ldw >= K && (uintptr_t)packed % 16 == 0, "dvis_x3_tile_pack: bad operands");
-  const int64_t pieces = (int64_t)N * K / 8;
-  hipLaunchKernelGGL(x3_tile_pack_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, ldw, N, K,
-                     ldexpf(1.f, wexp), (_Float16 *)packed, pieces, 0);
-  return dvis_check_launch("dvis_x3_tile_pack");
-}
-
-// The same image with the k slots of every k-tile in the order a row image's producer writes them (x3_tile_k): 0 natural (the
-// stand-alone and LayerNorm producers), 1 the GELU form of dvis_x3_tile_linear_image, 2 dvis_attention_x3_packed_image (K = heads * 64).
-DVIS_EXPORT int dvis_x3_tile_pack_order(const float *w, int64_t ldw, int N, int K, int wexp, int order, void *packed, void *stream) {
-  DVIS_REQUIRE(dvis_x3_tile_supported(N, K), "dvis_x3_tile_pack_order: N %% 256 == 0 and K %% 32 == 0 are required (N %d, K %d)", N, K);
-  DVIS_REQUIRE(w && packed && ldw >= K && (uintptr_t)packed % 16 == 0, "dvis_x3_tile_pack_order: bad operands");
-  DVIS_REQUIRE(order >= 0 && order <= 2 && (order != 2 || K % 64 == 0), "dvis_x3_tile_pack_order: order 0 .. 2 (2: K %% 64 == 0)");
+  DVIS_REQUIRE(order >= 0 && order <= 2 && (order != 2 || K % 64 == 0), "dvis_x3_tile_pack: order 0 .. 2 (2: K %% 64 == 0)");
   const int64_t pieces = (int64_t)N * K / 8;
   hipLaunchKernelGGL(x3_tile_pack_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, ldw, N, K,
                      ldexpf(1.f, wexp), (_Float16 *)packed, pieces, order);
-  return dvis_check_launch("dvis_x3_tile_pack_order");
+  return dvis_check_launch("dvis_x3_tile_pack");
 }
 
 // ---- row images (x3_tile_img_kernel above)

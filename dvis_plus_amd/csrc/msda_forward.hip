@@ -516,29 +516,29 @@ DVIS_EXPORT int dvis_msda_forward(int dtype, const void *value, const int64_t *s
 
 // Host side of the fused form for one storage type T: value, the raw offset / logit rows and the output in T (fp32, or fp16 /
 // bf16 — what nn.Linear hands over under autocast), reference points fp32, all arithmetic fp32.  Rows in the reference's
-// layout (all heads' offsets, then all heads' logits), strides in elements.  `who` names the entry in the error messages.
+// layout (all heads' offsets, then all heads' logits), strides in elements.
 template <typename T>
-static int fused_forward(const char *who, const void *value, const int64_t *shapes, const int64_t *level_start,
+static int fused_forward(const void *value, const int64_t *shapes, const int64_t *level_start,
                          const float *ref, int Nref, const void *offsets, int64_t off_stride, const void *logits,
                          int64_t logit_stride, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                          const int64_t *shapes_host, void *stream) {
   constexpr bool kF32 = sizeof(T) == 4;
-  DVIS_REQUIRE(N >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "%s: bad sizes", who);
+  DVIS_REQUIRE(N >= 0 && S > 0 && M > 0 && D > 0 && L > 0 && Lq >= 0 && P > 0, "msda_fused_forward: bad sizes");
   if (N == 0 || Lq == 0) return DVIS_OK;
-  DVIS_REQUIRE(value && shapes && level_start && ref && offsets && logits && out, "%s: null pointer", who);
-  DVIS_REQUIRE(Nref == 1 || Nref == N, "%s: Nref must be 1 or N", who);
+  DVIS_REQUIRE(value && shapes && level_start && ref && offsets && logits && out, "msda_fused_forward: null pointer");
+  DVIS_REQUIRE(Nref == 1 || Nref == N, "msda_fused_forward: Nref must be 1 or N");
   DVIS_REQUIRE(off_stride >= (int64_t)M * L * P * 2 && logit_stride >= (int64_t)M * L * P && off_stride % 4 == 0 &&
                    logit_stride % 4 == 0 && (L * P) % 4 == 0,
-               "%s: row strides must cover the rows (M*L*P*2 / M*L*P) and, like L*P, be multiples of 4 elements", who);
+               "msda_fused_forward: row strides must cover the rows (M*L*P*2 / M*L*P) and, like L*P, be multiples of 4 elements");
   // a set-up thread reads 4 logits at once: 16-byte rows in fp32, 8-byte rows in half; a lane gathers 16 bytes of `value`
   DVIS_REQUIRE((((uintptr_t)offsets | (uintptr_t)logits) & (kF32 ? 15u : 7u)) == 0 && aligned16(value) && aligned16(out) &&
                    (kF32 || (M * D) % 8 == 0),
-               "%s: %d-byte aligned rows and 16-byte aligned value / out required%s", who, kF32 ? 16 : 8,
+               "msda_fused_forward: %d-byte aligned rows and 16-byte aligned value / out required%s", kF32 ? 16 : 8,
                kF32 ? "" : ", M*D a multiple of 8");
-  DVIS_REQUIRE((size_t)S * M * D * sizeof(T) < 0x7fffffffu, "%s: frame slice >= 2 GiB", who);
+  DVIS_REQUIRE((size_t)S * M * D * sizeof(T) < 0x7fffffffu, "msda_fused_forward: frame slice >= 2 GiB");
   if constexpr (kF32)     // (the limit dvis_msda_fused_backward shares with its forward)
     DVIS_REQUIRE((size_t)Lq * (size_t)(off_stride > logit_stride ? off_stride : logit_stride) * sizeof(T) < 0x7fffffffu,
-                 "%s: one frame of offsets/logits must stay below 2 GiB", who);
+                 "msda_fused_forward: one frame of offsets/logits must stay below 2 GiB");
   // Encoder self-attention geometry (queries = the pixels of the L maps, shapes known on the host): 8 x 8 query tiles
   TileMap tm{};
   make_tile_map(shapes_host, L, Lq, &tm);
@@ -547,26 +547,21 @@ static int fused_forward(const char *who, const void *value, const int64_t *shap
                                         (const T *)logits, logit_stride, ref, Nref, N, S, M, Lq, (T *)out, (hipStream_t)stream,
                                         &handled, &tm);
   if (handled) return rc;
-  dvis_set_error("%s: unsupported (D=%d, L=%d, P=%d); supported D in {32,64}, (L,P) in {(1,4),(3,4),(4,4)}", who, D, L, P);
+  dvis_set_error("msda_fused_forward: unsupported (D=%d, L=%d, P=%d); supported D in {32,64}, (L,P) in {(1,4),(3,4),(4,4)}", D, L, P);
   return DVIS_E_UNSUPPORTED;
 }
 
-DVIS_EXPORT int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int64_t *level_start,
-                                        const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                                        const float *logits, int64_t logit_stride, int N, int S, int M, int D, int L,
-                                        int Lq, int P, float *out, const int64_t *shapes_host, void *stream) {
-  return fused_forward<float>("msda_fused_forward", value, shapes, level_start, ref, Nref, offsets, off_stride, logits,
-                              logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream);
-}
-
-DVIS_EXPORT int dvis_msda_fused_forward_h(int dtype, const void *value, const int64_t *shapes, const int64_t *level_start,
-                                          const float *ref, int Nref, const void *offsets, int64_t off_stride,
-                                          const void *logits, int64_t logit_stride, int N, int S, int M, int D, int L, int Lq,
-                                          int P, void *out, const int64_t *shapes_host, void *stream) {
-  DVIS_REQUIRE(dtype == DVIS_F16 || dtype == DVIS_BF16, "msda_fused_forward_h: dtype must be fp16 or bf16 (fp32: dvis_msda_fused_forward)");
+DVIS_EXPORT int dvis_msda_fused_forward(int dtype, const void *value, const int64_t *shapes, const int64_t *level_start,
+                                        const float *ref, int Nref, const void *offsets, int64_t off_stride,
+                                        const void *logits, int64_t logit_stride, int N, int S, int M, int D, int L, int Lq,
+                                        int P, void *out, const int64_t *shapes_host, void *stream) {
+  DVIS_REQUIRE(dtype == DVIS_F32 || dtype == DVIS_F16 || dtype == DVIS_BF16, "msda_fused_forward: dtype must be F32, F16 or BF16 (got %d)", dtype);
+  if (dtype == DVIS_F32)
+    return fused_forward<float>(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride, N, S, M, D, L, Lq,
+                                P, out, shapes_host, stream);
   return dtype == DVIS_F16
-             ? fused_forward<__half>("msda_fused_forward_h", value, shapes, level_start, ref, Nref, offsets, off_stride, logits,
-                                     logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream)
-             : fused_forward<__hip_bfloat16>("msda_fused_forward_h", value, shapes, level_start, ref, Nref, offsets, off_stride,
-                                             logits, logit_stride, N, S, M, D, L, Lq, P, out, shapes_host, stream);
+             ? fused_forward<__half>(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride, N, S, M, D, L,
+                                     Lq, P, out, shapes_host, stream)
+             : fused_forward<__hip_bfloat16>(value, shapes, level_start, ref, Nref, offsets, off_stride, logits, logit_stride, N, S,
+                                             M, D, L, Lq, P, out, shapes_host, stream);
 }

@@ -199,18 +199,13 @@ def msda_fused_forward(value, spatial_shapes, level_start_index, reference_point
     hs = None
     if shapes_host is not None:
         hs = (ctypes.c_int64 * (2 * L))(*[int(v) for hw in shapes_host for v in hw])
-    # fp16 / bf16 storage (what the projections produce under autocast) has an entry of its own, led by the dtype code
-    if value.dtype == torch.float32:
-        entry, lead = "dvis_msda_fused_forward", ()
-    else:
-        entry, lead = "dvis_msda_fused_forward_h", (native.dtype_code(value),)
     with torch.cuda.device(value.device):
-        rc = getattr(native.lib(), entry)(
-            *lead, native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
+        rc = native.lib().dvis_msda_fused_forward(
+            native.dtype_code(value), native.dev_ptr(value, "value"), native.dev_ptr(spatial_shapes, "spatial_shapes"),
             native.dev_ptr(level_start_index, "level_start_index"), native.dev_ptr(reference_points, "ref"), nref,
             ctypes.c_void_p(offsets.data_ptr()), offsets.stride(0), ctypes.c_void_p(logits.data_ptr()), logits.stride(0),
             N, S, M, D, L, Lq, P, native.dev_ptr(out, "out"), hs, native.stream_ptr(value.device))
-    native.check(rc, entry)
+    native.check(rc, "dvis_msda_fused_forward")
     return out
 
 
@@ -675,7 +670,7 @@ def _attention_kernel(q, k, v, nheads, mask=None, allowed_count=None, out=None, 
             ctypes.c_void_p(v.data_ptr()), _strides3(v, B, C, d), ctypes.c_void_p(out.data_ptr()),
             _strides3(out, B, C, d), mptr, aptr, B, nheads, Lq, Lk, d, 1.0 / (d ** 0.5),
             ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, native.stream_ptr(q.device), kern)
-    native.check(rc, "dvis_attention_forward")
+    native.check(rc, "dvis_attention_forward_k")
     return out
 
 
@@ -1264,21 +1259,18 @@ def add_layer_norm(x, res, norm, pos=None):
         rp, rs = ctypes.c_void_p(res.data_ptr()), C
     out = torch.empty_like(x)
     rows = x.numel() // C
+    pp, pos_rows, out_pos = None, 0, None
+    if pos is not None:
+        pos_rows = pos.numel() // C
+        if x.dim() != 3 or x.shape[1] != pos_rows or pos.dtype != torch.float32 or not pos.is_cuda:
+            raise RuntimeError("add_layer_norm: pos must be a float32 GPU (S, C) embedding for x of shape (N, S, C)")
+        pos = pos.contiguous()
+        pp, out_pos = native.dev_ptr(pos, "pos"), torch.empty_like(x)
     with torch.cuda.device(x.device):
-        if pos is None:
-            rc = native.lib().dvis_add_layernorm(ctypes.c_void_p(x.data_ptr()), rp, rs, native.dev_ptr(norm.weight, "gamma"),
-                                                 native.dev_ptr(norm.bias, "beta"), ctypes.c_void_p(out.data_ptr()),
-                                                 rows, C, float(norm.eps), native.stream_ptr(x.device))
-        else:
-            pos_rows = pos.numel() // C
-            if x.dim() != 3 or x.shape[1] != pos_rows or pos.dtype != torch.float32 or not pos.is_cuda:
-                raise RuntimeError("add_layer_norm: pos must be a float32 GPU (S, C) embedding for x of shape (N, S, C)")
-            pos = pos.contiguous()
-            out_pos = torch.empty_like(x)
-            rc = native.lib().dvis_add_layernorm_pos(
-                ctypes.c_void_p(x.data_ptr()), rp, rs, native.dev_ptr(norm.weight, "gamma"),
-                native.dev_ptr(norm.bias, "beta"), ctypes.c_void_p(out.data_ptr()), native.dev_ptr(pos, "pos"), pos_rows,
-                ctypes.c_void_p(out_pos.data_ptr()), rows, C, float(norm.eps), native.stream_ptr(x.device))
+        rc = native.lib().dvis_add_layernorm(
+            ctypes.c_void_p(x.data_ptr()), rp, rs, native.dev_ptr(norm.weight, "gamma"), native.dev_ptr(norm.bias, "beta"),
+            ctypes.c_void_p(out.data_ptr()), pp, pos_rows, None if pos is None else ctypes.c_void_p(out_pos.data_ptr()),
+            rows, C, float(norm.eps), native.stream_ptr(x.device))
     native.check(rc, "dvis_add_layernorm")
     return out if pos is None else (out, out_pos)
 
@@ -1360,16 +1352,12 @@ def upsample_add(lateral, top, lat_affine=None):
         return lateral + F.interpolate(top, size=(H, W), mode="bilinear", align_corners=False)
     top = top.contiguous()
     out = torch.empty_like(lateral)
+    scale, shift = (None, None) if lat_affine is None else (native.dev_ptr(lat_affine[0], "scale"),
+                                                            native.dev_ptr(lat_affine[1], "shift"))
     with torch.cuda.device(lateral.device):
-        if lat_affine is None:
-            rc = native.lib().dvis_upsample_add(native.dev_ptr(lateral, "lateral"), native.dev_ptr(top, "top"),
-                                                native.dev_ptr(out, "out"), N * C, H, W, top.shape[-2], top.shape[-1],
-                                                native.stream_ptr(lateral.device))
-        else:
-            rc = native.lib().dvis_upsample_add_affine(
-                native.dev_ptr(lateral, "lateral"), native.dev_ptr(lat_affine[0], "scale"),
-                native.dev_ptr(lat_affine[1], "shift"), native.dev_ptr(top, "top"), native.dev_ptr(out, "out"), N * C, H,
-                W, top.shape[-2], top.shape[-1], native.stream_ptr(lateral.device))
+        rc = native.lib().dvis_upsample_add(native.dev_ptr(lateral, "lateral"), scale, shift, native.dev_ptr(top, "top"),
+                                            native.dev_ptr(out, "out"), N * C, H, W, top.shape[-2], top.shape[-1],
+                                            native.stream_ptr(lateral.device))
     native.check(rc, "dvis_upsample_add")
     return out
 
@@ -1994,8 +1982,8 @@ def x3_tile_pack(weight, order=0):
         nbytes = native.lib().dvis_x3_tile_packed_bytes(N, K)
         if nbytes <= 0:
             raise RuntimeError(f"x3_tile_pack: weight {tuple(w.shape)} is not served (N % 256 == 0, K % 32 == 0)")
-        return _x3_packed(w, nbytes, lambda e, buf, st: native.lib().dvis_x3_tile_pack_order(
-            ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e, order, buf, st), "dvis_x3_tile_pack_order")
+        return _x3_packed(w, nbytes, lambda e, buf, st: native.lib().dvis_x3_tile_pack(
+            ctypes.c_void_p(w.data_ptr()), w.stride(0), N, K, e, order, buf, st), "dvis_x3_tile_pack")
     return _x3_cache(weight, [weight], make, kind="tile" if order == 0 else f"tile order {order}")
 
 
@@ -2071,12 +2059,7 @@ def x3_tile_linear(x, weight, bias, act=None, residual=None, xexp=None):
     x2, ldx = _x3_rows(x, "x")
     buf, wexp = x3_tile_pack(weight)
     out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
-    rptr, ldr = None, 0
-    if residual is not None:
-        if residual.shape != out.shape or residual.dtype != torch.float32 or not residual.is_cuda:
-            raise RuntimeError("x3_tile_linear: residual must be a float32 GPU tensor of the output's shape")
-        r2, ldr = _rows2d(residual, N)
-        rptr = ctypes.c_void_p(r2.data_ptr())
+    rptr, ldr = _x3_residual("x3_tile_linear", residual, out)
     with torch.cuda.device(x.device):
         native.check(native.lib().dvis_x3_tile_linear(
             ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0], K, ctypes.c_void_p(buf.data_ptr()), N,
@@ -2105,12 +2088,7 @@ def _x3_tile_linear_image(img, weight, bias, act, residual):
                                                        native.stream_ptr(img.device)), "dvis_x3_tile_linear_image")
             return RowImage(out, (*img.shape[:-1], N), X3_XEXP, 1)
         out = torch.empty((*img.shape[:-1], N), dtype=torch.float32, device=img.device)
-        rptr, ldr = None, 0
-        if residual is not None:
-            if residual.shape != out.shape or residual.dtype != torch.float32 or not residual.is_cuda:
-                raise RuntimeError("x3_tile_linear: residual must be a float32 GPU tensor of the output's shape")
-            r2, ldr = _rows2d(residual, N)
-            rptr = ctypes.c_void_p(r2.data_ptr())
+        rptr, ldr = _x3_residual("x3_tile_linear", residual, out)
         native.check(lib.dvis_x3_tile_linear_image(ctypes.c_void_p(img.data.data_ptr()), M, K, ctypes.c_void_p(buf.data_ptr()), N, img.exp, wexp,
                                                    bptr, {None: 0, "relu": 1}[act], rptr, ldr, ctypes.c_void_p(out.data_ptr()), N, None, 0,
                                                    native.stream_ptr(img.device)), "dvis_x3_tile_linear_image")
@@ -2198,73 +2176,51 @@ def x3_rows_in_place(x, N):
             and x.data_ptr() % 16 == 0)
 
 
-def _x3_linear_rows(x, weight, bias, relu, xexp, xadd):
-    N, K = weight.shape
-    B, S, _ = x.shape
-    buf, wexp = x3_pack(weight)
-    out = torch.empty((B, S, N), dtype=torch.float32, device=x.device)
-    lib = native.lib()
-    bptr = None if bias is None else native.dev_ptr(bias.detach(), "bias")
-    xe = X3_XEXP if xexp is None else xexp
-    with torch.cuda.device(x.device):
-        if xadd is not None:
-            if xadd.numel() != S * K or xadd.dtype != torch.float32 or not xadd.is_cuda:
-                raise RuntimeError("x3_linear: xadd must be a float32 GPU (S, K) embedding for x of shape (B, S, K)")
-            xadd = xadd.contiguous()
-            native.check(lib.dvis_x3_linear_add_rows(
-                ctypes.c_void_p(x.data_ptr()), K, S, x.stride(0), B * S, K, ctypes.c_void_p(buf.data_ptr()), N, xe, wexp,
-                ctypes.c_void_p(xadd.data_ptr()), S, bptr, int(relu), ctypes.c_void_p(out.data_ptr()), N,
-                native.stream_ptr(x.device)), "dvis_x3_linear_add_rows")
-        else:
-            native.check(lib.dvis_x3_linear_rows(
-                ctypes.c_void_p(x.data_ptr()), K, S, x.stride(0), B * S, K, ctypes.c_void_p(buf.data_ptr()), N, xe, wexp,
-                bptr, int(relu), ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device)), "dvis_x3_linear_rows")
-    return out
+def _x3_residual(op, residual, out, rows=_rows2d):
+    """(pointer, row stride) of the optional `residual` added to the fp32 GPU rows `out`; (None, 0) without one."""
+    if residual is None:
+        return None, 0
+    if residual.shape != out.shape or residual.dtype != torch.float32 or not residual.is_cuda:
+        raise RuntimeError(f"{op}: residual must be a float32 GPU tensor of the output's shape")
+    r2, ldr = rows(residual, out.shape[-1])
+    return ctypes.c_void_p(r2.data_ptr()), ldr
 
 
 def x3_linear(x, weight, bias, relu=False, xexp=None, xadd=None, act=None, residual=None):
     """``relu?((x + xadd) @ weight.T + bias)`` through dvis_x3_linear[_add]; with act ("gelu" | "relu" | None) / residual:
     ``act(x @ weight.T + bias) + residual`` through dvis_x3_linear_res (GELU and the residual add inside the GEMM's epilogue).  x (..., K) float32 GPU; weight (N, K); xadd: None or
     a (1, S, 256) / (S, 256) embedding for x of shape (B, S, 256), broadcast over B — added inside the kernel while it builds the
-    row's fragments, the sum is never written (K = 256, any N the kernels serve: all passes over N run from one read of the row)."""
+    row's fragments, the sum is never written (K = 256, any N the kernels serve: all passes over N run from one read of the row).
+    A (B, S, K) slice of a longer tensor (``x3_rows_in_place``) is read where it lies: dvis_x3_linear_rows / _add_rows."""
     N, K = weight.shape
-    if act is None and residual is None and x3_rows_in_place(x, N):
-        return _x3_linear_rows(x, weight, bias, relu, xexp, xadd)
-    x2, ldx = _x3_rows(x, "x")
+    in_place = act is None and residual is None and x3_rows_in_place(x, N)
+    if in_place:        # x, row stride, rows per batch entry, batch stride, rows
+        xargs = (ctypes.c_void_p(x.data_ptr()), K, x.shape[1], x.stride(0), x.shape[0] * x.shape[1])
+    else:
+        x2, ldx = _x3_rows(x, "x")
+        xargs = (ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0])
     buf, wexp = x3_pack(weight)
     out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
+    wargs = (K, ctypes.c_void_p(buf.data_ptr()), N, X3_XEXP if xexp is None else xexp, wexp)
+    bptr = None if bias is None else native.dev_ptr(bias.detach(), "bias")
+    oargs = (ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device))
     if act is not None or residual is not None:
         if xadd is not None:
             raise RuntimeError("x3_linear: xadd and act / residual are served by different entry points")
         code = {None: int(bool(relu)), "relu": 1, "gelu": 2}[act]
-        rptr, ldr = None, 0
-        if residual is not None:
-            if residual.shape != out.shape or residual.dtype != torch.float32 or not residual.is_cuda:
-                raise RuntimeError("x3_linear: residual must be a float32 GPU tensor of the output's shape")
-            r2, ldr = _x3_rows(residual, "residual")
-            rptr = ctypes.c_void_p(r2.data_ptr())
-        with torch.cuda.device(x.device):
-            native.check(native.lib().dvis_x3_linear_res(
-                ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0], K, ctypes.c_void_p(buf.data_ptr()), N,
-                X3_XEXP if xexp is None else xexp, wexp, None if bias is None else native.dev_ptr(bias.detach(), "bias"), code,
-                rptr, ldr, ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device)), "dvis_x3_linear_res")
-        return out
-    if xadd is not None:
+        entry = "dvis_x3_linear_res"
+        extra = (bptr, code, *_x3_residual("x3_linear", residual, out, rows=lambda r, _: _x3_rows(r, "residual")))
+    elif xadd is not None:
         if x.dim() != 3 or xadd.numel() != x.shape[1] * K or xadd.dtype != torch.float32 or not xadd.is_cuda:
             raise RuntimeError("x3_linear: xadd must be a float32 GPU (S, K) embedding for x of shape (B, S, K)")
         xadd = xadd.contiguous()
-        with torch.cuda.device(x.device):
-            native.check(native.lib().dvis_x3_linear_add(
-                ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0], K, ctypes.c_void_p(buf.data_ptr()), N,
-                X3_XEXP if xexp is None else xexp, wexp, ctypes.c_void_p(xadd.data_ptr()), x.shape[1],
-                None if bias is None else native.dev_ptr(bias.detach(), "bias"), int(relu), ctypes.c_void_p(out.data_ptr()), N,
-                native.stream_ptr(x.device)), "dvis_x3_linear_add")
-        return out
+        entry = "dvis_x3_linear_add_rows" if in_place else "dvis_x3_linear_add"
+        extra = (ctypes.c_void_p(xadd.data_ptr()), x.shape[1], bptr, int(relu))
+    else:
+        entry = "dvis_x3_linear_rows" if in_place else "dvis_x3_linear"
+        extra = (bptr, int(relu))
     with torch.cuda.device(x.device):
-        native.check(native.lib().dvis_x3_linear(
-            ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0], K, ctypes.c_void_p(buf.data_ptr()), N,
-            X3_XEXP if xexp is None else xexp, wexp, None if bias is None else native.dev_ptr(bias.detach(), "bias"), int(relu),
-            ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device)), "dvis_x3_linear")
+        native.check(getattr(native.lib(), entry)(*xargs, *wargs, *extra, *oargs), entry)
     return out
 
 
@@ -2356,12 +2312,12 @@ def maps_to_tokens(maps, affines=None, pos=None):
     with torch.cuda.device(out.device):
         for m, a in zip(maps, affines):
             HW = m.shape[2] * m.shape[3]
-            rc = native.lib().dvis_nchw_to_tokens_affine(
+            rc = native.lib().dvis_nchw_to_tokens(
                 ctypes.c_void_p(m.data_ptr()), None if a is None else native.dev_ptr(a[0], "scale"),
                 None if a is None else native.dev_ptr(a[1], "shift"), pp, ctypes.c_void_p(out.data_ptr()),
                 None if out_pos is None else ctypes.c_void_p(out_pos.data_ptr()), N, C, HW, S, row0,
                 native.stream_ptr(out.device))
-            native.check(rc, "dvis_nchw_to_tokens_affine")
+            native.check(rc, "dvis_nchw_to_tokens")
             row0 += HW
     return out if pos is None else (out, out_pos)
 
@@ -2897,6 +2853,14 @@ def _s2_weights(weight):
                       "dvis_conv3x3s2_pack")
 
 
+def _library_conv_bias_act(x, weight, bias, relu, stride, padding):
+    """The library convolution, then the in-place ``bias_act_`` pass unless there is nothing to add."""
+    y = torch.nn.functional.conv2d(x, weight, None, stride, padding)
+    if bias is None and not relu:
+        return y
+    return bias_act_(y, None if bias is None else bias.detach(), None, relu)
+
+
 def conv3x3s2_bias_act(x, weight, bias=None, relu=False, own=None):
     """relu?(conv2d(x, weight (K, C, 3, 3), stride 2, padding 1) + bias[k]) on NCHW.  own=True: the direct fp32-MFMA kernel
     (csrc/conv3x3s2.hip: 119 - 131 TFLOP/s at the R50 shapes, 1.4 - 1.65x the library + epilogue pass), raising when the
@@ -2921,10 +2885,7 @@ def conv3x3s2_bias_act(x, weight, bias=None, relu=False, own=None):
                 native.dev_ptr(out, "out"), N, C, K, H, W, 1 if relu else 0, native.stream_ptr(x.device))
         native.check(rc, "dvis_conv3x3s2")
         return out
-    y = torch.nn.functional.conv2d(x, weight, None, 2, 1)
-    if bias is None and not relu:
-        return y
-    return bias_act_(y, None if bias is None else bias.detach(), None, relu)
+    return _library_conv_bias_act(x, weight, bias, relu, 2, 1)
 
 
 def conv7x7s2_stem(x, weight, bias=None, relu=False, own=None):
@@ -2947,10 +2908,7 @@ def conv7x7s2_stem(x, weight, bias=None, relu=False, own=None):
                                              native.dev_ptr(out, "out"), N, H, W, 1 if relu else 0, native.stream_ptr(x.device))
         native.check(rc, "dvis_conv7x7s2")
         return out
-    y = torch.nn.functional.conv2d(x, weight, None, 2, 3)
-    if bias is None and not relu:
-        return y
-    return bias_act_(y, None if bias is None else bias.detach(), None, relu)
+    return _library_conv_bias_act(x, weight, bias, relu, 2, 3)
 
 
 def conv3x3_bias_act(x, weight, bias=None, relu=False, winograd=None):
@@ -2982,10 +2940,7 @@ def conv3x3_bias_act(x, weight, bias=None, relu=False, winograd=None):
                     1 if relu else 0, native.stream_ptr(x.device))
             native.check(rc, "dvis_conv3x3_winograd")
             return out
-    y = torch.nn.functional.conv2d(x, weight, None, 1, 1)
-    if bias is None and not relu:
-        return y
-    return bias_act_(y, None if bias is None else bias.detach(), None, relu)
+    return _library_conv_bias_act(x, weight, bias, relu, 1, 1)
 
 
 def bias_act_(x, bias=None, res=None, relu=True):

@@ -28,12 +28,10 @@ SIGNATURES = {
     "dvis_msda_backward_det": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dvis_msda_fused_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_msda_fused_backward": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
-    "dvis_msda_fused_forward": (_i, [_p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "dvis_msda_fused_forward_h": (_i, [_i, _p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "dvis_nchw_to_tokens": (_i, [_p, _p, _i64, _i, _i64, _i64, _i64, _p]),
+    "dvis_msda_fused_forward": (_i, [_i, _p, _p, _p, _p, _i, _p, _i64, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "dvis_nchw_to_tokens": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p]),
     "dvis_tokens_to_nchw": (_i, [_p, _p, _i64, _i, _i64, _i64, _i64, _p]),
     "dvis_normalize_pad": (_i, [_p, _i, _p, _i64, _i, _i, _i, _i, _i, _p, _p, _p]),
-    "dvis_nchw_to_tokens_affine": (_i, [_p, _p, _p, _p, _p, _p, _i64, _i, _i64, _i64, _i64, _p]),
     "dvis_mask_logits": (_i, [_p, _p, _i, _i, _i, _i64, _p, _p]),
     "dvis_mask_logits_backward_ws_bytes": (_i64, [_i, _i, _i, _i64]),
     "dvis_mask_logits_backward": (_i, [_p, _p, _i, _i, _i, _i64, _p, _p, _p, _p]),
@@ -41,18 +39,15 @@ SIGNATURES = {
     "dvis_center_pool3": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p]),
     "dvis_attn_mask_pooled": (_i, [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "dvis_mask_gemm_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _i]),
-    "dvis_attention_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_attention_ws_bytes_k": (_i64, [_i, _i, _i, _i, _i]),
     "dvis_attention_plan": (_i, [_i, _i, _i, _i, _i, _i64, _i64, _i, _p]),
-    "dvis_attention_forward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p]),
     "dvis_attention_forward_k": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _i]),
     "dvis_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
     "dvis_attention_backward_threads": (_i, [_i]),
     "dvis_masked_attention_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_masked_attention_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p]),
     "dvis_masked_attention_backward_plan": (_i, [_i, _i, _i, _p]),
-    "dvis_add_layernorm": (_i, [_p, _p, _i64, _p, _p, _p, _i64, _i, _f, _p]),
-    "dvis_add_layernorm_pos": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i, _f, _p]),
+    "dvis_add_layernorm": (_i, [_p, _p, _i64, _p, _p, _p, _p, _i64, _p, _i64, _i, _f, _p]),
     "dvis_bias_act": (_i, [_p, _p, _p, _i64, _i, _i64, _i, _p]),
     "dvis_conv3x3_winograd_supported": (_i, [_i, _i, _i, _i]),
     "dvis_conv3x3_winograd_pack": (_i, [_p, _p, _i, _i, _p]),
@@ -73,8 +68,7 @@ SIGNATURES = {
     "dvis_group_norm_affine": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i64, _f, _p]),
     "dvis_scale_shift_act": (_i, [_p, _p, _p, _i64, _i64, _i, _p]),
     "dvis_group_norm_finalize": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i64, _f, _p]),
-    "dvis_upsample_add_affine": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
-    "dvis_upsample_add": (_i, [_p, _p, _p, _i64, _i, _i, _i, _i, _p]),
+    "dvis_upsample_add": (_i, [_p, _p, _p, _p, _p, _i64, _i, _i, _i, _i, _p]),
     "dvis_dwconv3x3_tokens": (_i, [_p, _p, _i64, _i, _i, _i, _i, _p, _p, _i, _p]),
     "dvis_dwconv3x3_tokens_backward_ws_bytes": (_i64, [_i, _i, _i, _i]),
     "dvis_dwconv3x3_tokens_backward": (_i, [_p, _p, _p, _p, _i, _i64, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
@@ -103,13 +97,12 @@ SIGNATURES = {
     "dvis_x3_linear": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _i, _p, _i64, _p]),
     "dvis_x3_tile_supported": (_i, [_i, _i]),
     "dvis_x3_tile_packed_bytes": (_i64, [_i, _i]),
-    "dvis_x3_tile_pack": (_i, [_p, _i64, _i, _i, _i, _p, _p]),
+    "dvis_x3_tile_pack": (_i, [_p, _i64, _i, _i, _i, _i, _p, _p]),
     "dvis_x3_tile_linear_qkv": (_i, [_p, _i64, _i64, _i, _p, _i, _i, _i, _p, _i, _i, _f, _p, _p]),
     "dvis_attention_x3_packed": (_i, [_p, _p, _p, _i, _i, _i, _p]),
     "dvis_x3_rows_image_bytes": (_i64, [_i64, _i]),
     "dvis_x3_rows_image": (_i, [_p, _i64, _i64, _i, _i, _p, _p]),
     "dvis_layernorm_rows_image": (_i, [_p, _p, _p, _i64, _i, _f, _i, _p, _p]),
-    "dvis_x3_tile_pack_order": (_i, [_p, _i64, _i, _i, _i, _i, _p, _p]),
     "dvis_x3_tile_linear_image": (_i, [_p, _i64, _i, _p, _i, _i, _i, _p, _i, _p, _i64, _p, _i64, _p, _i, _p]),
     "dvis_x3_tile_linear_qkv_image": (_i, [_p, _i64, _i, _p, _i, _i, _i, _p, _i, _i, _f, _p, _p]),
     "dvis_attention_x3_packed_image": (_i, [_p, _p, _i, _i, _i, _i, _p]),

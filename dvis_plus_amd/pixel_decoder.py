@@ -164,7 +164,7 @@ class MSDeformAttn(nn.Module):
         fast = self._fast_path_ok(query, reference_points, input_padding_mask)
         # half-precision storage (a .half() / .bfloat16() module, or fp32 parameters under torch.autocast — how the reference
         # evaluates, train_net_video.py:259): the projections come out in fp16 / bf16 and the fused kernel takes them as they
-        # are (dvis_msda_fused_forward_h)
+        # are (dvis_msda_fused_forward with their dtype code)
         lowp = query.dtype != torch.float32 or torch.is_autocast_enabled()
         # the tall projections on the F16 matrix cores with split fp32 operands (csrc/gemm_x3.hip)
         x3 = fast and Fn.x3_on() and not lowp and Fn.x3_ok(input_flatten, self.d_model, self.d_model) \

@@ -20,7 +20,7 @@
  *                               dvis_Plus/tracker.py:379 and dvis_Plus/video_mask2former_transformer_decoder.py:363
  *   dvis_attn_mask           <- einsum + F.interpolate + (sigmoid < 0.5) of forward_prediction_heads, ibid. :363-371,
  *                               plus the "fully masked row" reset at :297
- *   dvis_attention_forward   <- nn.MultiheadAttention core (softmax(QK^T/sqrt(d) [+mask]) V) as used by
+ *   dvis_attention_forward_k <- nn.MultiheadAttention core (softmax(QK^T/sqrt(d) [+mask]) V) as used by
  *                               CrossAttentionLayer / SelfAttentionLayer (mask2former_video/.../video_mask2former_transformer_decoder.py:18-136),
  *                               ReferringCrossAttentionLayer (dvis_Plus/tracker.py:8-92), TemporalRefiner (dvis_Plus/refiner.py:104-139)
  *   dvis_attention_backward  <- autograd's backward of that core without a mask (training of the temporal refiner,
@@ -39,7 +39,7 @@
  *   dvis_conv7x7s2           <- the 7x7 / stride 2 stem convolution of the R50 (detectron2 BasicStem.conv1)
  *   dvis_bias_relu_maxpool   <- FrozenBN shift + ReLU + max_pool2d(3, stride 2, padding 1) of the ResNet stem (detectron2 BasicStem)
  *   dvis_upsample_add        <- `cur_fpn + F.interpolate(out[-1], size=..., mode="bilinear")`, msdeformattn.py:347
- *   dvis_group_norm_affine / dvis_scale_shift_act / dvis_upsample_add_affine
+ *   dvis_group_norm_affine / dvis_scale_shift_act
  *                            <- the GroupNorm (+ReLU) of detectron2's Conv2d wrapper around the FPN lateral / output
  *                               convolutions, msdeformattn.py:280-300 (built) and :343-349 (applied)
  *   dvis_vps_argmax          <- two-stage resize + sigmoid + score-weighted argmax + segment areas of inference_video_vps,
@@ -144,19 +144,22 @@ int dvis_msda_backward_det(const float *value, const int64_t *shapes, const int6
                            float *grad_w, void *ws, void *stream);
 
 /*
- * Fused forward (fp32): takes the RAW outputs of the sampling_offsets / attention_weights linears.
- *   offsets  rows of (M, L, P, 2) floats, row stride `off_stride` floats, one row per (n, q)
- *   logits   rows of (M, L*P)     floats, row stride `logit_stride` floats
+ * Fused forward: takes the RAW outputs of the sampling_offsets / attention_weights linears.  `value`, the offset / logit rows and
+ * `out` in `dtype`: DVIS_F32, or DVIS_F16 / DVIS_BF16 storage (what the projections of MSDeformAttn.forward,
+ * ops/modules/ms_deform_attn.py:97-105, produce under torch.autocast, how the reference evaluates: train_net_video.py:259; 8
+ * channels per lane; the reference's own op dispatches float / double only, ms_deform_attn_cuda.cu:69, and its module falls into
+ * the grid_sample path there); reference points and arithmetic fp32 in every case.
+ *   offsets  rows of (M, L, P, 2) elements, row stride `off_stride` elements, one row per (n, q)
+ *   logits   rows of (M, L*P)     elements, row stride `logit_stride` elements
  *   ref      (Nref, Lq, L, 2) reference points; Nref == 1 broadcasts over the batch
  * loc = ref[:, :, None, :, None, :] + offsets / (W_l, H_l);  w = softmax over (L*P) — ms_deform_attn.py:101-109.
  *   shapes_host: NULL, or a HOST copy of `shapes`; when given and sum(H_l*W_l) == Lq == S (encoder self-attention:
  *   the queries are the pixels) blocks own 8x8 pixel tiles instead of 64 consecutive queries (cache locality only;
  *   results are identical).
  */
-int dvis_msda_fused_forward(const float *value, const int64_t *shapes, const int64_t *level_start,
-                            const float *ref, int Nref, const float *offsets, int64_t off_stride,
-                            const float *logits, int64_t logit_stride,
-                            int N, int S, int M, int D, int L, int Lq, int P, float *out,
+int dvis_msda_fused_forward(int dtype, const void *value, const int64_t *shapes, const int64_t *level_start,
+                            const float *ref, int Nref, const void *offsets, int64_t off_stride, const void *logits,
+                            int64_t logit_stride, int N, int S, int M, int D, int L, int Lq, int P, void *out,
                             const int64_t *shapes_host, void *stream);
 
 /*
@@ -176,18 +179,6 @@ int dvis_msda_fused_backward(const float *value, const int64_t *shapes, const in
                              const float *offsets, int64_t off_stride, const float *logits, int64_t logit_stride,
                              const float *grad_out, int N, int S, int M, int D, int L, int Lq, int P, float *grad_value,
                              float *grad_offsets, float *grad_logits, void *ws, void *stream);
-
-/*
- * dvis_msda_fused_forward on HALF-PRECISION storage: `value`, the raw offset / logit rows and `out` in `dtype` (DVIS_F16 /
- * DVIS_BF16 — what the projections of MSDeformAttn.forward, ops/modules/ms_deform_attn.py:97-105, produce under
- * torch.autocast, how the reference evaluates: train_net_video.py:259), reference points fp32, arithmetic fp32, 8 channels
- * per lane.  The reference's own op dispatches float / double only (ms_deform_attn_cuda.cu:69) and its module falls into the
- * grid_sample path there.  Row strides in ELEMENTS; the reference's row layout (all heads' offsets, then all heads' logits).
- */
-int dvis_msda_fused_forward_h(int dtype, const void *value, const int64_t *shapes, const int64_t *level_start,
-                              const float *ref, int Nref, const void *offsets, int64_t off_stride, const void *logits,
-                              int64_t logit_stride, int N, int S, int M, int D, int L, int Lq, int P, void *out,
-                              const int64_t *shapes_host, void *stream);
 
 /*
  * Mask logits: out[b, q, p] = sum_c embed[b, q, c] * feat[b, c, p]     (fp32, exact-fp32 MFMA)
@@ -218,7 +209,7 @@ int dvis_mask_logits_backward(const float *g, const float *feat, int B, int R, i
  *   blocked = logits < 0  (== sigmoid < 0.5).
  *   embed (B, Q, C), feat (B, C, H, W)  ->  mask (B, Q, h*w) uint8 (1 = blocked), one copy (not per head);
  *   allowed_count (B, Q) int32 = number of un-blocked keys per row (zeroed inside).  A row with count 0 is
- *   "blocked everywhere": dvis_attention_forward then ignores the mask for that row, which is the reference's
+ *   "blocked everywhere": dvis_attention_forward_k then ignores the mask for that row, which is the reference's
  *   reset `attn_mask[where(attn_mask.sum(-1) == HW)] = False` (:297) without its host sync.
  */
 int dvis_attn_mask(const float *embed, const float *feat, int B, int Q, int C, int H, int W, int h, int w,
@@ -254,17 +245,12 @@ int dvis_mask_gemm_plan(int mode, int B, int Q, int C, int H, int W, int h, int 
  *   projections and out be the (Lq, B, heads*d) buffer the out-projection reads.)
  *   mask: NULL or uint8 (B, Lq, Lk), 1 = blocked, shared by the heads of a batch entry (4-byte aligned).
  *   allowed_count: NULL or int32 (B, Lq) from dvis_attn_mask; rows with count 0 ignore the mask.
- *   ws: workspace of dvis_attention_ws_bytes(B*heads, Lq, Lk, d) bytes (split-K partials); may be NULL when 0.
+ *   ws: workspace of dvis_attention_ws_bytes_k(B*heads, Lq, Lk, d, kernel) bytes (split-K partials); may be NULL when 0.
+ *   kernel: 0 = chosen from the sizes; or chosen by the CALLER: 1 = the short-key latency kernel (Lk <= 128: one workgroup per
+ *   (batch, head, 16-query tile), K / V staged in one memory round trip), 2 = below.  A (batch, head)'s result depends on the
+ *   kernel, so a caller that needs the same bits for a clip whether it runs alone or batched with others (the referring
+ *   tracker's recurrence, dvis_Plus/tracker.py:277-318) pins it.
  */
-int64_t dvis_attention_ws_bytes(int BH, int Lq, int Lk, int d);
-int dvis_attention_forward(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
-                           const float *v, const int64_t *v_strides, float *out, const int64_t *o_strides,
-                           const uint8_t *mask, const int32_t *allowed_count, int B, int heads, int Lq, int Lk,
-                           int d, float scale, void *ws, void *stream);
-/* Same with the kernel chosen by the CALLER instead of from the sizes: 0 = dvis_attention_forward's choice, 1 = the
- * short-key latency kernel (Lk <= 128: one workgroup per (batch, head, 16-query tile), K / V staged in one memory round
- * trip).  A (batch, head)'s result depends on the kernel, so a caller that needs the same bits for a clip whether it runs
- * alone or batched with others (the referring tracker's recurrence, dvis_Plus/tracker.py:277-318) pins it. */
 int dvis_attention_forward_k(const float *q, const int64_t *q_strides, const float *k, const int64_t *k_strides,
                            const float *v, const int64_t *v_strides, float *out, const int64_t *o_strides,
                            const uint8_t *mask, const int32_t *allowed_count, int B, int heads, int Lq, int Lk,
@@ -296,7 +282,7 @@ int dvis_attention_plan(int BH, int Lq, int Lk, int d, int has_mask, int64_t k_r
  *   P = softmax(Q K^T * scale)   dV = P^T dO   dP = dO V^T   D = rowsum(P o dP)   dS = P o (dP - D)
  *   dQ = scale * dS K            dK = scale * dS^T Q
  * The probabilities are recomputed from q and k; nothing of the forward is needed.
- *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward (x_strides[3] =
+ *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward_k (x_strides[3] =
  *   {batch, head, row} in floats, d contiguous, 16-byte aligned, strides multiples of 4 floats); d in {32, 64}; 1 <= Lk <= 256.
  *   dq (Lq, B, heads * d), dk / dv (Lk, B, heads * d): contiguous outputs.
  * One workgroup per (batch entry, head) walks the queries in chunks of 16 in ascending order, so the sums of dK / dV over the
@@ -317,7 +303,7 @@ int dvis_attention_backward_threads(int Lk);
  *   P = softmax over the allowed keys   dV = P^T dO   dP = dO V^T   D = rowsum(P o dP)   dS = P o (dP - D)
  *   dQ = scale * dS K                   dK = scale * dS^T Q
  * P is recomputed from q and k, and D from that P: nothing of the forward is needed.
- *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward (x_strides[3] =
+ *   q / grad_out (B, heads, Lq, d), k / v (B, heads, Lk, d) as STRIDED views as in dvis_attention_forward_k (x_strides[3] =
  *   {batch, head, row} in floats, d contiguous, 16-byte aligned, strides multiples of 4 floats); d in {32, 64};
  *   1 <= Lq <= 256, 1 <= Lk <= 65536.
  *   mask: NULL or uint8 (B, Lq, Lk), 1 = blocked, shared by the heads (rows need no alignment); a blocked key has P = 0 exactly.
@@ -344,39 +330,34 @@ int dvis_masked_attention_backward_plan(int Lq, int Lk, int d, int32_t *plan);
 /*
  * out[r, :] = LayerNorm(x[r, :] + res[r, :]) * gamma + beta, rows x C fp32 (C % 4 == 0, C <= 1024); `res` may be NULL
  * and may have its own row stride (floats).  One pass: 2 reads + 1 write (torch: add kernel + layer_norm kernel).
+ * pos / out_pos (both or neither; then pos_rows > 0): a second output  out_pos[r, :] = out[r, :] + pos[r mod pos_rows, :]
+ * (pos: pos_rows x C): the deformable encoder's next-layer query `with_pos_embed(src, pos)` (msdeformattn.py:121-123 /
+ * ms_deform_attn.py:108) is written while the row is still in registers instead of by an add kernel of its own.
  */
 int dvis_add_layernorm(const float *x, const float *res, int64_t res_row_stride, const float *gamma, const float *beta,
-                       float *out, int64_t rows, int C, float eps, void *stream);
-
-/*
- * dvis_add_layernorm with a second output  out_pos[r, :] = out[r, :] + pos[r mod pos_rows, :]  (pos: pos_rows x C): the
- * deformable encoder's next-layer query `with_pos_embed(src, pos)` (msdeformattn.py:121-123 / ms_deform_attn.py:108) is
- * written while the row is still in registers instead of by an add kernel of its own.
- */
-int dvis_add_layernorm_pos(const float *x, const float *res, int64_t res_row_stride, const float *gamma, const float *beta,
-                           float *out, const float *pos, int64_t pos_rows, float *out_pos, int64_t rows, int C, float eps,
-                           void *stream);
+                       float *out, const float *pos, int64_t pos_rows, float *out_pos, int64_t rows, int C, float eps,
+                       void *stream);
 
 /*
  * out = lateral + F.interpolate(top, size=(H, W), mode="bilinear", align_corners=False) for `planes` = N*C planes;
  * lateral / out (planes, H, W), top (planes, h, w); W % 4 == 0.  (FPN top-down step, msdeformattn.py:347.)
+ * lat_scale / lat_shift (both or neither; per plane, from dvis_group_norm_affine): the lateral operand is read as
+ * lateral * scale + shift — the lateral convolution's GroupNorm applied on the fly (msdeformattn.py:345-347).
  */
-int dvis_upsample_add(const float *lateral, const float *top, float *out, int64_t planes, int H, int W, int h, int w,
-                      void *stream);
+int dvis_upsample_add(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top, float *out,
+                      int64_t planes, int H, int W, int h, int w, void *stream);
 
 /*
  * out[n][row0 + p][c] = x[n][c][p]: lays an (N, C, HW) map down as HW rows of an (N, S, C) token matrix — the
  * flatten(2).transpose(1, 2) + torch.cat over levels of MSDeformAttnTransformerEncoderOnly.forward
  * (mask2former/modeling/pixel_decoder/msdeformattn.py:64-79).  x contiguous (N, C, HW), out contiguous (N, S, C).
- */
-int dvis_nchw_to_tokens(const float *x, float *out, int64_t N, int C, int64_t HW, int64_t S, int64_t row0, void *stream);
-
-/*
- * dvis_nchw_to_tokens with the map read as x[n][c] * scale[n*C + c] + shift[n*C + c] (the input projection's GroupNorm,
- * msdeformattn.py:231-247, from dvis_group_norm_affine; NULL pair = identity) and an optional second output
+ * scale / shift: the map is read as x[n][c] * scale[n*C + c] + shift[n*C + c] (the input projection's GroupNorm,
+ * msdeformattn.py:231-247, from dvis_group_norm_affine; NULL pair = identity).  pos / out_pos: a second output
  * out_pos[n][row0 + p][c] = out[n][row0 + p][c] + pos[row0 + p][c] (pos: (S, C) token-major position + level embedding;
  * the first encoder layer's query, msdeformattn.py:121-123; NULL pair = not written).
  */
+int dvis_nchw_to_tokens(const float *x, const float *scale, const float *shift, const float *pos, float *out, float *out_pos,
+                        int64_t N, int C, int64_t HW, int64_t S, int64_t row0, void *stream);
 /* The way back for one level: out (N, C, HW) = tok[:, row0 : row0 + HW, :] transposed (tok: (N, S, C)) — the encoder output
  * as the map the FPN's top-down path reads, msdeformattn.py:333-339 (+ :347). */
 int dvis_tokens_to_nchw(const float *tok, float *out, int64_t N, int C, int64_t HW, int64_t S, int64_t row0, void *stream);
@@ -386,8 +367,6 @@ int dvis_tokens_to_nchw(const float *tok, float *out, int64_t N, int C, int64_t 
  * (is_u8 = 1) or fp32 planes, planes = frames * C.  The same fp32 subtract and divide as the torch expression: same bits. */
 int dvis_normalize_pad(const void *in, int is_u8, float *out, int64_t planes, int C, int H, int W, int Hp, int Wp, const float *mean,
                        const float *stdv, void *stream);
-int dvis_nchw_to_tokens_affine(const float *x, const float *scale, const float *shift, const float *pos, float *out,
-                               float *out_pos, int64_t N, int C, int64_t HW, int64_t S, int64_t row0, void *stream);
 
 /*
  * 1x1 stride-1 convolution on NCHW with its epilogue in one pass (exact-fp32 MFMA):
@@ -467,8 +446,7 @@ int dvis_bias_relu_maxpool(const float *x, const float *bias, float *out, int64_
  *                           affine  scale[n*C + c] = rstd * gamma[c],  shift[n*C + c] = beta[c] - mean * scale
  *                           (gamma / beta may be NULL = 1 / 0);  (C / G) * HW % 4 == 0, x 16-byte aligned;
  *   dvis_scale_shift_act    in place x[plane] = relu?(x[plane] * scale[plane] + shift[plane]) — GroupNorm (+ReLU) applied;
- *   dvis_upsample_add_affine  as dvis_upsample_add with the lateral operand read as lateral * scale + shift — the
- *                           lateral convolution's GroupNorm applied on the fly (msdeformattn.py:345-347).
+ *                           (or on the fly: the lat_scale / lat_shift of dvis_upsample_add).
  */
 int dvis_group_norm_affine(const float *x, const float *gamma, const float *beta, float *scale, float *shift, int64_t N,
                            int C, int G, int64_t HW, float eps, void *stream);
@@ -478,8 +456,6 @@ int dvis_scale_shift_act(float *x, const float *scale, const float *shift, int64
  * gn_part: (N, G, HW / 32, 2) doubles) instead of a read of the map: the same formula and casts; HW % 32 == 0, C / G <= 64. */
 int dvis_group_norm_finalize(const double *part, const float *gamma, const float *beta, float *scale, float *shift, int64_t N, int C,
                              int G, int64_t HW, float eps, void *stream);
-int dvis_upsample_add_affine(const float *lateral, const float *lat_scale, const float *lat_shift, const float *top,
-                             float *out, int64_t planes, int H, int W, int h, int w, void *stream);
 
 /*
  * Depthwise 3 x 3 convolution (padding 1) + bias (+ exact GELU) on a TOKEN-major map: the ConvFFN of the ViT-Adapter extractors
@@ -732,12 +708,13 @@ int dvis_x3_linear_res(const float *x, int64_t ldx, int64_t M, int K, const void
  * 128 tokens x 256 features with BOTH operands staged through LDS (the rows split into their two f16 terms once per tile), so a
  * row tile is read once per 256 output features from the L2 of the XCD that owns it — the streaming kernels above re-read and
  * re-split it per pass from HBM.  N % 256 == 0, K % 32 == 0 (dvis_x3_tile_supported); weights packed once with dvis_x3_tile_pack
- * into dvis_x3_tile_packed_bytes(N, K) bytes (the LDS image per (feature tile, k-step of 16), scaled by 2^wexp).
+ * into dvis_x3_tile_packed_bytes(N, K) bytes (the LDS image per (feature tile, k-step of 16), scaled by 2^wexp; order 0, or the
+ * order of a row image's producer, below).
  * A row's result does not depend on M.  Same range guard as the other split-f16 kernels.
  */
 int dvis_x3_tile_supported(int N, int K);
 int64_t dvis_x3_tile_packed_bytes(int N, int K);
-int dvis_x3_tile_pack(const float *w, int64_t ldw, int N, int K, int wexp, void *packed, void *stream);
+int dvis_x3_tile_pack(const float *w, int64_t ldw, int N, int K, int wexp, int order, void *packed, void *stream);
 int dvis_x3_tile_linear(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias, int act,
                         const float *res, int64_t ldres, float *out, int64_t ldo, void *stream);
 /* The ViT blocks' fused qkv projection + attention operands (backbones_vitAdapter attention: `qkv = self.qkv(x)`, then softmax(q k^T
@@ -745,7 +722,7 @@ int dvis_x3_tile_linear(const float *x, int64_t ldx, int64_t M, int K, const voi
  * and writes, instead of the fp32 qkv tensor, the two-term f16 operand images of the split-f16 attention kernel into `ws`
  * (dvis_attention_ws_bytes_k(B * heads, L, L, 64, 2) bytes; rows of x = B batch entries of L tokens; qscale = softmax scale x log2(e)
  * x 2^4); dvis_attention_x3_packed then runs that kernel's main launch on `ws` (out: (B, heads, L, 64) view, strides in floats as in
- * dvis_attention_forward).  Saves the 1.36 GB qkv tensor's write + re-read and the pack launch per block. */
+ * dvis_attention_forward_k).  Saves the 1.36 GB qkv tensor's write + re-read and the pack launch per block. */
 int dvis_x3_tile_linear_qkv(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias,
                             int heads, int L, float qscale, void *ws, void *stream);
 int dvis_attention_x3_packed(const void *ws, float *out, const int64_t *o_strides, int B, int heads, int L, void *stream);
@@ -757,7 +734,7 @@ int dvis_attention_x3_packed(const void *ws, float *out, const int64_t *o_stride
  *   producers: dvis_x3_rows_image (fp32 rows; k order 0), dvis_layernorm_rows_image (LayerNorm of fp32 rows, C <= 1024; order 0),
  *              dvis_x3_tile_linear_image with act = 2 (GELU; order 1), dvis_attention_x3_packed_image (order 2);
  *   consumers: dvis_x3_tile_linear_image (act 0 / 1: fp32 rows out, + residual), dvis_x3_tile_linear_qkv_image; their weights
- *              packed with dvis_x3_tile_pack_order(order of the image's producer): the k slots of a k-tile are a free permutation
+ *              packed with dvis_x3_tile_pack(order of the image's producer): the k slots of a k-tile are a free permutation
  *              as long as both operands use the same one.
  * Rows past M of the last row tile are written as zeros by every producer.  Results per row as dvis_x3_tile_linear (the same three
  * products per k-tile, fp32 accumulate; orders 1 / 2 add the k-tile's terms in another order).
@@ -766,7 +743,6 @@ int64_t dvis_x3_rows_image_bytes(int64_t M, int K);
 int dvis_x3_rows_image(const float *x, int64_t ldx, int64_t M, int K, int xexp, void *image, void *stream);
 int dvis_layernorm_rows_image(const float *x, const float *gamma, const float *beta, int64_t M, int C, float eps, int xexp, void *image,
                               void *stream);
-int dvis_x3_tile_pack_order(const float *w, int64_t ldw, int N, int K, int wexp, int order, void *packed, void *stream);
 int dvis_x3_tile_linear_image(const void *ximg, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias, int act,
                               const float *res, int64_t ldres, float *out, int64_t ldo, void *oimg, int oexp, void *stream);
 int dvis_x3_tile_linear_qkv_image(const void *ximg, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias, int heads,
@@ -843,7 +819,7 @@ int dvis_conv1x1_x3_image(const float *x, const void *packed, const float *bias,
  * per 64-channel chunk and lane instead of 32 of 4 bytes, no split arithmetic in the loop.
  *   dvis_conv_x3_pack_image  weights (K, C, taps 1 | 9) for an image-INPUT launch (channels of a chunk in accumulator order)
  *   dvis_conv_x3_image       relu?(conv + bias + res): ximg | x in, image | y out (at least one image); K = 128 or K % 256 == 0
- *   dvis_upsample_add_image  dvis_upsample_add[_affine] with the sum written as an operand image (the FPN's top-down path)
+ *   dvis_upsample_add_image  dvis_upsample_add with the sum written as an operand image (the FPN's top-down path)
  */
 int64_t dvis_conv_x3_image_bytes(int64_t N, int C, int H, int W);
 int dvis_conv_x3_pack_image(const float *w, int K, int C, int taps, int wexp, void *packed, void *stream);

@@ -143,6 +143,59 @@ def test_add_layernorm_second_output_with_position_embedding():
     assert torch.equal(out_pos, out + pos.to(DEV))
 
 
+def test_add_layernorm_first_output_does_not_depend_on_the_position_output():
+    """One entry serves both forms: the rows written with `pos` given are, bit for bit, the rows written without it, and the
+    second output is their sum with the embedding.  10 rows of 8: three workgroups of four rows, the last one half empty."""
+    from dvis_plus_amd.functions import add_layer_norm
+    g = torch.Generator().manual_seed(13)
+    x, r, pos = (torch.randn(*s, generator=g).to(DEV) for s in ((2, 5, 8), (2, 5, 8), (1, 5, 8)))
+    ln = torch.nn.LayerNorm(8).to(DEV)
+    with torch.no_grad():
+        alone = add_layer_norm(x, r, ln)
+        out, out_pos = add_layer_norm(x, r, ln, pos=pos)
+        ref = ln(x + r)
+    assert torch.equal(out, alone) and torch.equal(out_pos, out + pos)
+    torch.testing.assert_close(out, ref, rtol=1e-5, atol=5e-6)
+
+
+def test_upsample_add_with_and_without_lateral_affine_at_a_ragged_width():
+    """(1, 4, 6, 10) from (3, 5) — W % 4 != 0: the scalar form, which no other test runs with an affine — against the torch
+    formulation of the front-end's own torch path.  Tolerance: the operands are O(4), the kernel contracts `lateral * scale +
+    shift` and the four bilinear taps in another order than torch: a few fp32 ulps of 4 (5e-7 each), inside 1e-5."""
+    from dvis_plus_amd.functions import upsample_add
+    g = torch.Generator().manual_seed(17)
+    lat, top = torch.randn(1, 4, 6, 10, generator=g).to(DEV), torch.randn(1, 4, 3, 5, generator=g).to(DEV)
+    scale, shift = (torch.randn(4, generator=g) * 0.3 + 1).to(DEV), torch.randn(4, generator=g).to(DEV)
+    with torch.no_grad():
+        up = F.interpolate(top, size=(6, 10), mode="bilinear", align_corners=False)
+        torch.testing.assert_close(upsample_add(lat, top), lat + up, rtol=1e-5, atol=1e-5)
+        torch.testing.assert_close(upsample_add(lat, top, (scale, shift)),
+                                   lat * scale.view(1, 4, 1, 1) + shift.view(1, 4, 1, 1) + up, rtol=1e-5, atol=1e-5)
+
+
+def test_merged_entries_refuse_half_given_operand_pairs():
+    """dvis_add_layernorm with pos but no out_pos, or with pos_rows = 0, and dvis_upsample_add with a scale and no shift return an
+    error code before any launch: the message names the entry and the output is not written."""
+    import ctypes
+    from dvis_plus_amd import native
+    lib, st = native.lib(), native.stream_ptr(torch.device(DEV))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    x, gamma, beta, pos = (torch.ones(*s, device=DEV) for s in ((10, 8), (8,), (8,), (5, 8)))
+    out, out_pos = torch.full((10, 8), -7.0, device=DEV), torch.full((10, 8), -7.0, device=DEV)
+    for pos_rows, op in ((5, None), (0, p(out_pos))):
+        with pytest.raises(RuntimeError, match="dvis_add_layernorm failed.*pos and out_pos are given together"):
+            native.check(lib.dvis_add_layernorm(p(x), None, 0, p(gamma), p(beta), p(out), p(pos), pos_rows, op, 10, 8, 1e-5, st),
+                         "dvis_add_layernorm")
+    with pytest.raises(RuntimeError, match="dvis_add_layernorm failed.*pos and out_pos are given together"):
+        native.check(lib.dvis_add_layernorm(p(x), None, 0, p(gamma), p(beta), p(out), None, 5, p(out_pos), 10, 8, 1e-5, st),
+                     "dvis_add_layernorm")
+    lat, top, scale = torch.ones(1, 4, 6, 10, device=DEV), torch.ones(1, 4, 3, 5, device=DEV), torch.ones(4, device=DEV)
+    res = torch.full((1, 4, 6, 10), -7.0, device=DEV)
+    with pytest.raises(RuntimeError, match="dvis_upsample_add failed.*scale and shift come together"):
+        native.check(lib.dvis_upsample_add(p(lat), p(scale), None, p(top), p(res), 4, 6, 10, 3, 5, st), "dvis_upsample_add")
+    assert bool((out == -7).all()) and bool((out_pos == -7).all()) and bool((res == -7).all())
+
+
 def test_maps_to_tokens_with_group_norm_and_position_output():
     from dvis_plus_amd import functions as Fn
     g = torch.Generator().manual_seed(5)

@@ -210,6 +210,27 @@ def test_fused_forward_half_precision_storage(dt, rel, M, D, shapes, Lq):
         msda_fused_forward(vd, s.to(DEV), lsi.to(DEV), rd, pf[:, :n_off], pf[:, n_off:n_off + M * L * P], L, P)
 
 
+def test_fused_forward_refuses_a_dtype_code_it_does_not_serve():
+    """dvis_msda_fused_forward takes its storage type as a code: F64 (served by dvis_msda_forward alone) is an error code before
+    any launch, reported under the entry's name."""
+    import ctypes
+    from dvis_plus_amd import native
+    N, M, D, L, P, shapes = 1, 8, 32, 1, 4, [(4, 5)]
+    s, lsi = level_tensors(shapes)
+    S = Lq = 20
+    value = torch.zeros(N, S, M, D, dtype=torch.float64, device=DEV)
+    proj = torch.zeros(N * Lq, M * L * P * 3, dtype=torch.float64, device=DEV)
+    ref, out = torch.zeros(1, Lq, L, 2, device=DEV), torch.full((N, Lq, M * D), -7.0, dtype=torch.float64, device=DEV)
+    sd, ld = s.to(DEV), lsi.to(DEV)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    rc = native.lib().dvis_msda_fused_forward(
+        native.F64, p(value), p(sd), p(ld), p(ref), 1, p(proj), proj.stride(0), p(proj[:, M * L * P * 2:]), proj.stride(0), N, S, M, D,
+        L, Lq, P, p(out), None, native.stream_ptr(torch.device(DEV)))
+    with pytest.raises(RuntimeError, match="dvis_msda_fused_forward failed.*dtype must be F32, F16 or BF16"):
+        native.check(rc, "dvis_msda_fused_forward")
+    assert bool((out == -7).all())
+
+
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 def test_msdeformattn_module_under_autocast_takes_the_fused_half_kernel(dt):
     """How the reference evaluates (train_net_video.py:259: torch.autocast): fp32 parameters, projections in half precision.
@@ -225,16 +246,16 @@ def test_msdeformattn_module_under_autocast_takes_the_fused_half_kernel(dt):
     src = torch.randn(2, S, 256, device=DEV)
     ref = torch.rand(1, S, 3, 2, device=DEV)
     lib = native.lib()
-    orig, calls = lib.dvis_msda_fused_forward_h, []
+    orig, calls = lib.dvis_msda_fused_forward, []
     try:
-        lib.dvis_msda_fused_forward_h = lambda *a: (calls.append(a[0]), orig(*a))[1]
+        lib.dvis_msda_fused_forward = lambda *a: (calls.append(a[0]), orig(*a))[1]
         with torch.no_grad():
             want = attn(src, ref, src, s.to(DEV), lsi.to(DEV), None, spatial_shapes_py=shapes)
             with torch.autocast("cuda", dtype=dt):
                 got = attn(src, ref, src, s.to(DEV), lsi.to(DEV), None, spatial_shapes_py=shapes)
     finally:
-        lib.dvis_msda_fused_forward_h = orig
-    assert calls == [native.F16 if dt == torch.float16 else native.BF16] and got.dtype == dt
+        lib.dvis_msda_fused_forward = orig
+    assert calls == [native.F32, native.F16 if dt == torch.float16 else native.BF16] and got.dtype == dt
     tol = 2.0 ** (-7 if dt == torch.float16 else -4) * float(want.abs().max())
     assert float((got.float() - want).abs().max()) <= tol
 

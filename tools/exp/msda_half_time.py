@@ -1,4 +1,4 @@
-"""Fused MSDeformAttn at the pixel decoder's shape (30 frames of 720p): fp32 vs fp16 / bf16 storage (dvis_msda_fused_forward_h)."""
+"""Fused MSDeformAttn at the pixel decoder's shape (30 frames of 720p): fp32 vs fp16 / bf16 storage (the dtype codes of dvis_msda_fused_forward)."""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from dvis_plus_amd.functions import msda_fused_forward

@@ -89,8 +89,8 @@ for tag, path in libs:
     log2d = logits.view(N * Lq, -1)
 
     def fused():
-        rc = l.dvis_msda_fused_forward(p(value), p(shapes), p(lsi), p(ref), 1, p(offs2d), offs2d.stride(0), p(log2d),
-                                       log2d.stride(0), N, S, M, D, L, Lq, P, p(out), HOST_SHAPES, st)
+        rc = l.dvis_msda_fused_forward(native.F32, p(value), p(shapes), p(lsi), p(ref), 1, p(offs2d), offs2d.stride(0),
+                                       p(log2d), log2d.stride(0), N, S, M, D, L, Lq, P, p(out), HOST_SHAPES, st)
         assert rc == 0
     ms = timeit(fused)
     err = (out - ref_out).abs().max().item()
