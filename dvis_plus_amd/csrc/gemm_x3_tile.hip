@@ -174,17 +174,67 @@ __device__ __forceinline__ void tile_store_rows(const TileArgs &a, f16v (&acc)[2
   if (a.flag != nullptr && chk != chk) atomicCAS(a.flag, 0, a.tag);
 }
 
+// ---- what the two tiled kernels share: a workgroup's tile with a lane's place in it, and a wave's view of a stage's fragments
+// with the six products of an accumulator block.  Their pipelines stay apart (below).
+
+// Workgroup -> (row tile mt, column tile nt): the eight workgroups of consecutive blockIdx (one per XCD) hold eight row tiles of
+// one column tile, and an XCD meets its row tile again with the next column tile.  Wave = (wm, wn) of 2 x 2; lane = (r, g).
+struct TileCoord {
+  int tid, lane, wave, r, g, wm, wn, mt, nt, KT;
+  int64_t m0;
+  __device__ __forceinline__ TileCoord(const TileArgs &a) {
+    tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    r = lane & 31, g = lane >> 5;
+    wm = wave >> 1, wn = wave & 1;
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    mt = (slot / a.tn) * 8 + xcd, nt = slot - (slot / a.tn) * a.tn;
+    m0 = (int64_t)mt * k2TM;
+    KT = a.K / k2TK;
+  }
+  // a workgroup past the last row tile (the grid is a multiple of eight row tiles): the kernel returns at once
+  __device__ __forceinline__ bool outside(const TileArgs &a) const { return mt >= a.tm; }
+};
+
+// A wave's fragments of a stage: B blocks one after the other (each serves the two A blocks), the next block's pair requested
+// (load_b into the other buffer) before the current block's six products.
+struct TileFragments {
+  int aoff, boff;
+  h8 ah[2], al[2], bh[2], bl[2];
+  __device__ __forceinline__ TileFragments(const TileCoord &c)
+      : aoff((c.wm * 64 + c.r) * 16 + c.g * k2ChunkA), boff(2 * k2PartA + (c.wn * 128 + c.r) * 16 + c.g * k2ChunkB) {}
+  __device__ __forceinline__ void load_a(const char *s) {
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb) {
+      const char *p = s + aoff + mb * 512;
+      ah[mb] = *(const h8 *)p, al[mb] = *(const h8 *)(p + k2PartA);
+    }
+  }
+  __device__ __forceinline__ void load_b(const char *s, int nb, int buf) {
+    const char *p = s + boff + nb * 512;
+    bh[buf] = *(const h8 *)p, bl[buf] = *(const h8 *)(p + k2PartB);
+  }
+  // The six products of accumulator block nb: lo x hi, hi x lo, hi x hi (the small terms first) for the two A blocks against the
+  // B pair in buffer nb & 1.  SWAP: B as the first operand — a lane then holds one token and sixteen features of a block (the
+  // image-writing epilogue of x3_tile_img_kernel<2>).  The callers keep a sched_barrier(0) on either side.
+  template <bool SWAP>
+  __device__ __forceinline__ void products(f16v (&acc)[2][4], int nb) const {
+    auto mfma = [&](int mb, h8 x, h8 w) {
+      acc[mb][nb] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_f16(w, x, acc[mb][nb], 0, 0, 0)
+                         : __builtin_amdgcn_mfma_f32_32x32x16_f16(x, w, acc[mb][nb], 0, 0, 0);
+    };
+    mfma(0, al[0], bh[nb & 1]), mfma(1, al[1], bh[nb & 1]);
+    mfma(0, ah[0], bl[nb & 1]), mfma(1, ah[1], bl[nb & 1]);
+    mfma(0, ah[0], bh[nb & 1]), mfma(1, ah[1], bh[nb & 1]);
+  }
+};
+
 template <bool GELU, bool PACK = false>
 __global__ __launch_bounds__(256, 2) void x3_tile_kernel(TileArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, g = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int mt = (slot / a.tn) * 8 + xcd, nt = slot - (slot / a.tn) * a.tn;
-  if (mt >= a.tm) return;
-  const int64_t m0 = (int64_t)mt * k2TM;
-  const int KT = a.K / k2TK;
+  const TileCoord c(a);
+  if (c.outside(a)) return;
+  const int tid = c.tid, lane = c.lane, wave = c.wave, nt = c.nt, KT = c.KT;
+  const int64_t m0 = c.m0;
 
   // staging: A row tid >> 1, k-chunk tid & 1 (8 floats), two k-tiles ahead in registers; B by LDS-DMA (16 pieces of 1 KB, 4 per wave)
   const int aq = tid & 1;
@@ -230,23 +280,9 @@ __global__ __launch_bounds__(256, 2) void x3_tile_kernel(TileArgs a) {
   stash_a(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  const int aoff = (wm * 64 + r) * 16 + g * k2ChunkA, boff = 2 * k2PartA + (wn * 128 + r) * 16 + g * k2ChunkB;
-  // fragments: B blocks one after the other (each serves the two A blocks), the next block's pair requested before the
-  // current block's six products
-  h8 ah[2], al[2], bh[2], bl[2];
-  auto load_a = [&](const char *s) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      const char *p = s + aoff + mb * 512;
-      ah[mb] = *(const h8 *)p, al[mb] = *(const h8 *)(p + k2PartA);
-    }
-  };
-  auto load_b = [&](const char *s, int nb, int buf) {
-    const char *p = s + boff + nb * 512;
-    bh[buf] = *(const h8 *)p, bl[buf] = *(const h8 *)(p + k2PartB);
-  };
-  load_a(lds);
-  load_b(lds, 0, 0);
+  TileFragments f(c);
+  f.load_a(lds);
+  f.load_b(lds, 0, 0);
   auto tile = [&](int kt, auto set_c) {
     constexpr int SET = decltype(set_c)::value;      // tile kt + 1 is in set SET; tile kt + 2 goes to set SET ^ 1
     if (kt + 1 < KT) dma_b(kt + 1);
@@ -254,14 +290,9 @@ __global__ __launch_bounds__(256, 2) void x3_tile_kernel(TileArgs a) {
     const char *s = lds + (kt & 1) * k2Stage;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-      if (nb + 1 < 4) load_b(s, nb + 1, (nb + 1) & 1);
+      if (nb + 1 < 4) f.load_b(s, nb + 1, (nb + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
-      acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[0], bh[nb & 1], acc[0][nb], 0, 0, 0);
-      acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[1], bh[nb & 1], acc[1][nb], 0, 0, 0);
-      acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0], bl[nb & 1], acc[0][nb], 0, 0, 0);
-      acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1], bl[nb & 1], acc[1][nb], 0, 0, 0);
-      acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0], bh[nb & 1], acc[0][nb], 0, 0, 0);
-      acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1], bh[nb & 1], acc[1][nb], 0, 0, 0);
+      f.template products<false>(acc, nb);
       if (nb == 1 && kt + 1 < KT) stash_a((kt + 1) & 1, SET);
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -272,8 +303,8 @@ __global__ __launch_bounds__(256, 2) void x3_tile_kernel(TileArgs a) {
     __syncthreads();
     if (kt + 1 < KT) {
       const char *sn = lds + ((kt + 1) & 1) * k2Stage;
-      load_a(sn);
-      load_b(sn, 0, 0);
+      f.load_a(sn);
+      f.load_b(sn, 0, 0);
     }
   };
   for (int kt = 0; kt < KT; kt += 2) {
@@ -282,9 +313,9 @@ __global__ __launch_bounds__(256, 2) void x3_tile_kernel(TileArgs a) {
   }
 
   if constexpr (PACK)
-    tile_store_qkv(a, acc, nt, wm, wn, r, g, m0);
+    tile_store_qkv(a, acc, nt, c.wm, c.wn, c.r, c.g, m0);
   else
-    tile_store_rows<GELU>(a, acc, nt, wm, wn, r, g, m0);
+    tile_store_rows<GELU>(a, acc, nt, c.wm, c.wn, c.r, c.g, m0);
 }
 
 // ---- Row-image forms.  The row operand arrives pre-split (its producer's epilogue held the values anyway): both operands are
@@ -298,14 +329,10 @@ constexpr int kRowTile = 8192;                       // bytes of one (row tile, 
 template <int MODE>
 __global__ __launch_bounds__(256, 2) void x3_tile_img_kernel(TileArgs a) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, g = lane >> 5;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const int mt = (slot / a.tn) * 8 + xcd, nt = slot - (slot / a.tn) * a.tn;
-  if (mt >= a.tm) return;
-  const int64_t m0 = (int64_t)mt * k2TM;
-  const int KT = a.K / k2TK;
+  const TileCoord c(a);
+  if (c.outside(a)) return;
+  const int lane = c.lane, wave = c.wave, r = c.r, g = c.g, wm = c.wm, wn = c.wn, mt = c.mt, nt = c.nt, KT = c.KT;
+  const int64_t m0 = c.m0;
   const x3_u4 rsa = x3_stream_rsrc(a.ximg + (size_t)mt * KT * kRowTile), rsb = x3_stream_rsrc(a.wp + (size_t)nt * KT * 16384);
   const unsigned lane16 = lane * 16, lds0 = lds_address(lds);
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
@@ -341,44 +368,18 @@ __global__ __launch_bounds__(256, 2) void x3_tile_img_kernel(TileArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   __syncthreads();
-  const int aoff = (wm * 64 + r) * 16 + g * k2ChunkA, boff = 2 * k2PartA + (wn * 128 + r) * 16 + g * k2ChunkB;
-  h8 ah[2], al[2], bh[2], bl[2];
-  auto load_a = [&](const char *s) {
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb) {
-      const char *p = s + aoff + mb * 512;
-      ah[mb] = *(const h8 *)p, al[mb] = *(const h8 *)(p + k2PartA);
-    }
-  };
-  auto load_b = [&](const char *s, int nb, int buf) {
-    const char *p = s + boff + nb * 512;
-    bh[buf] = *(const h8 *)p, bl[buf] = *(const h8 *)(p + k2PartB);
-  };
-  load_a(lds);
-  load_b(lds, 0, 0);
+  TileFragments f(c);
+  f.load_a(lds);
+  f.load_b(lds, 0, 0);
   int st = 0;                                       // stage of k-tile kt
   for (int kt = 0; kt < KT; ++kt) {
     if (kt + 2 < KT) dma(kt + 2, st == 0 ? 2 : st - 1);       // (the stage k-tile kt - 1 was read from: released by the last barrier)
     const char *s = lds + st * k2Stage;
 #pragma unroll
     for (int nb = 0; nb < 4; ++nb) {
-      if (nb + 1 < 4) load_b(s, nb + 1, (nb + 1) & 1);
+      if (nb + 1 < 4) f.load_b(s, nb + 1, (nb + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
-      if constexpr (MODE == 2) {
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[nb & 1], al[0], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[nb & 1], al[1], acc[1][nb], 0, 0, 0);
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[nb & 1], ah[0], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[nb & 1], ah[1], acc[1][nb], 0, 0, 0);
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[nb & 1], ah[0], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[nb & 1], ah[1], acc[1][nb], 0, 0, 0);
-      } else {
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[0], bh[nb & 1], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[1], bh[nb & 1], acc[1][nb], 0, 0, 0);
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0], bl[nb & 1], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1], bl[nb & 1], acc[1][nb], 0, 0, 0);
-        acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[0], bh[nb & 1], acc[0][nb], 0, 0, 0);
-        acc[1][nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[1], bh[nb & 1], acc[1][nb], 0, 0, 0);
-      }
+      f.template products<MODE == 2>(acc, nb);
       __builtin_amdgcn_sched_barrier(0);
     }
     if (kt + 2 < KT)
@@ -389,8 +390,8 @@ __global__ __launch_bounds__(256, 2) void x3_tile_img_kernel(TileArgs a) {
     st = st == 2 ? 0 : st + 1;
     if (kt + 1 < KT) {
       const char *sn = lds + st * k2Stage;
-      load_a(sn);
-      load_b(sn, 0, 0);
+      f.load_a(sn);
+      f.load_b(sn, 0, 0);
     }
   }
 
@@ -574,11 +575,15 @@ DVIS_EXPORT int dvis_layernorm_rows_image(const float *x, const float *gamma, co
   return dvis_check_launch("layernorm_rows_image_kernel");
 }
 
-static int tile_img_args(TileArgs &a, const void *ximg, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias,
-                         const char *who) {
+// ---- the tiled GEMM's four entries: tile_args fills what every form passes, tile_launch launches; an entry adds its own
+// operands and checks.  `rows`: the row operand, fp32 rows or row image.  The row-image entries call it first: its two operand
+// checks are theirs.  The fp32-row entries call it after their own, stricter checks (kept for their messages and order), so there
+// only "too many tiles" can fire.
+static int tile_args(TileArgs &a, const char *who, const void *rows, int64_t M, int K, const void *wp, int N, int xexp, int wexp,
+                     const float *bias) {
   DVIS_REQUIRE(dvis_x3_tile_supported(N, K), "%s: N %% 256 == 0 and K %% 32 == 0 are required (N %d, K %d)", who, N, K);
-  DVIS_REQUIRE(ximg && wp && M >= 0 && ((uintptr_t)ximg | (uintptr_t)wp) % 16 == 0, "%s: null or misaligned operand", who);
-  a.ximg = (const char *)ximg, a.M = M, a.K = K, a.N = N, a.wp = (const char *)wp;
+  DVIS_REQUIRE(rows && wp && M >= 0 && ((uintptr_t)rows | (uintptr_t)wp) % 16 == 0, "%s: null or misaligned operand", who);
+  a.M = M, a.K = K, a.N = N, a.wp = (const char *)wp;
   a.xscale = ldexpf(1.f, xexp), a.inv = ldexpf(1.f, -(xexp + wexp));
   a.bias = bias;
   const X3Guard gd = dvis_x3_guard();
@@ -589,45 +594,48 @@ static int tile_img_args(TileArgs &a, const void *ximg, int64_t M, int K, const 
   return DVIS_OK;
 }
 
+// One workgroup per (row tile, column tile), the row tiles rounded up to eight (one per XCD).  The kernel is a template argument:
+// every instantiation has its own LDS opt-in table.  A failing opt-in is reported under the kernel's `name`, a failing launch as `what`.
+template <void (*Kernel)(TileArgs)>
+static int tile_launch(size_t lds_bytes, const char *name, const char *what, const TileArgs &a, void *stream) {
+  static DvisLdsOptIn opted;
+  if (const int rc = dvis_lds_opt_in((const void *)Kernel, lds_bytes, &opted, name)) return rc;
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)((a.tm + 7) / 8 * 8 * a.tn)), dim3(256), lds_bytes, (hipStream_t)stream, a);
+  return dvis_check_launch(what);
+}
+
 // dvis_x3_tile_linear with the rows given as a row image.  act 0 / 1: fp32 rows out (+ residual); act 2 (GELU): the result as the
 // row image `oimg` (dvis_x3_rows_image_bytes(M, N) bytes, x 2^oexp, k order 1) of the GEMM that follows — `out` is not written.
 DVIS_EXPORT int dvis_x3_tile_linear_image(const void *ximg, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias, int act,
                                           const float *res, int64_t ldres, float *out, int64_t ldo, void *oimg, int oexp, void *stream) {
   TileArgs a = {};
-  if (const int rc = tile_img_args(a, ximg, M, K, wp, N, xexp, wexp, bias, "dvis_x3_tile_linear_image")) return rc;
+  if (const int rc = tile_args(a, "dvis_x3_tile_linear_image", ximg, M, K, wp, N, xexp, wexp, bias)) return rc;
   DVIS_REQUIRE(act >= 0 && act <= 2, "dvis_x3_tile_linear_image: act must be 0 (none), 1 (ReLU) or 2 (GELU -> row image)");
   if (M == 0) return DVIS_OK;
-  const unsigned grid = (unsigned)((a.tm + 7) / 8 * 8 * a.tn);
-  static DvisLdsOptIn o0, o2;
+  a.ximg = (const char *)ximg;
   if (act == 2) {
     DVIS_REQUIRE(oimg && (uintptr_t)oimg % 16 == 0 && res == nullptr, "dvis_x3_tile_linear_image: the GELU form writes a row image (no residual)");
     DVIS_REQUIRE(bias == nullptr || (uintptr_t)bias % 16 == 0, "dvis_x3_tile_linear_image: bias must be 16-byte aligned");
     a.oimg = (char *)oimg, a.oscale = ldexpf(1.f, oexp);
-    if (const int rc = dvis_lds_opt_in((const void *)x3_tile_img_kernel<2>, k3Lds, &o2, "x3_tile_img_kernel")) return rc;
-    hipLaunchKernelGGL(x3_tile_img_kernel<2>, dim3(grid), dim3(256), k3Lds, (hipStream_t)stream, a);
-  } else {
-    DVIS_REQUIRE(out && ldo >= N && (res == nullptr || ldres >= N), "dvis_x3_tile_linear_image: bad output / residual");
-    a.radd = res, a.ldres = ldres, a.out = out, a.ldo = ldo, a.act = act;
-    if (const int rc = dvis_lds_opt_in((const void *)x3_tile_img_kernel<0>, k3Lds, &o0, "x3_tile_img_kernel")) return rc;
-    hipLaunchKernelGGL(x3_tile_img_kernel<0>, dim3(grid), dim3(256), k3Lds, (hipStream_t)stream, a);
+    return tile_launch<x3_tile_img_kernel<2>>(k3Lds, "x3_tile_img_kernel", "x3_tile_img_kernel", a, stream);
   }
-  return dvis_check_launch("x3_tile_img_kernel");
+  DVIS_REQUIRE(out && ldo >= N && (res == nullptr || ldres >= N), "dvis_x3_tile_linear_image: bad output / residual");
+  a.radd = res, a.ldres = ldres, a.out = out, a.ldo = ldo, a.act = act;
+  return tile_launch<x3_tile_img_kernel<0>>(k3Lds, "x3_tile_img_kernel", "x3_tile_img_kernel", a, stream);
 }
 
 // dvis_x3_tile_linear_qkv with the rows given as a row image.
 DVIS_EXPORT int dvis_x3_tile_linear_qkv_image(const void *ximg, int64_t M, int K, const void *wp, int N, int xexp, int wexp, const float *bias,
                                               int heads, int L, float qscale, void *ws, void *stream) {
   TileArgs a = {};
-  if (const int rc = tile_img_args(a, ximg, M, K, wp, N, xexp, wexp, bias, "dvis_x3_tile_linear_qkv_image")) return rc;
+  if (const int rc = tile_args(a, "dvis_x3_tile_linear_qkv_image", ximg, M, K, wp, N, xexp, wexp, bias)) return rc;
   DVIS_REQUIRE(heads > 0 && N == 3 * heads * 64, "dvis_x3_tile_linear_qkv_image: N must be 3 * heads * 64 (N %d, heads %d)", N, heads);
   DVIS_REQUIRE(ws && (uintptr_t)ws % 16 == 0 && L >= 32 && M % L == 0, "dvis_x3_tile_linear_qkv_image: rows must be whole batch entries of L >= 32 tokens (M %lld, L %d)",
                (long long)M, L);
   if (M == 0) return DVIS_OK;
+  a.ximg = (const char *)ximg;
   a.pack_ws = (_Float16 *)ws, a.pack_heads = heads, a.pack_L = L, a.pack_qscale = qscale;
-  static DvisLdsOptIn o1;
-  if (const int rc = dvis_lds_opt_in((const void *)x3_tile_img_kernel<1>, k3Lds, &o1, "x3_tile_img_kernel")) return rc;
-  hipLaunchKernelGGL(x3_tile_img_kernel<1>, dim3((unsigned)((a.tm + 7) / 8 * 8 * a.tn)), dim3(256), k3Lds, (hipStream_t)stream, a);
-  return dvis_check_launch("x3_tile_img_kernel (qkv pack)");
+  return tile_launch<x3_tile_img_kernel<1>>(k3Lds, "x3_tile_img_kernel", "x3_tile_img_kernel (qkv pack)", a, stream);
 }
 
 // The ViT blocks' qkv projection writing the split-f16 attention kernel's operand images directly (no fp32 qkv tensor, no pack
@@ -640,20 +648,10 @@ DVIS_EXPORT int dvis_x3_tile_linear_qkv(const float *x, int64_t ldx, int64_t M, 
   DVIS_REQUIRE(((uintptr_t)x | (uintptr_t)wp | (uintptr_t)ws) % 16 == 0 && ldx % 4 == 0 && ldx >= K, "dvis_x3_tile_linear_qkv: 16-byte alignment, ldx %% 4 == 0");
   if (M == 0) return DVIS_OK;
   TileArgs a = {};
-  a.x = x, a.ldx = ldx, a.M = M, a.K = K, a.N = N, a.wp = (const char *)wp;
-  a.xscale = ldexpf(1.f, xexp), a.inv = ldexpf(1.f, -(xexp + wexp));
-  a.bias = bias;
+  if (const int rc = tile_args(a, "dvis_x3_tile_linear_qkv", x, M, K, wp, N, xexp, wexp, bias)) return rc;
+  a.x = x, a.ldx = ldx;
   a.pack_ws = (_Float16 *)ws, a.pack_heads = heads, a.pack_L = L, a.pack_qscale = qscale;
-  const X3Guard gd = dvis_x3_guard();
-  a.flag = gd.flag, a.tag = gd.tag;
-  const int64_t tm = (M + k2TM - 1) / k2TM;
-  a.tm = (int)tm, a.tn = N / kTN;
-  const int64_t grid = (tm + 7) / 8 * 8 * a.tn;
-  DVIS_REQUIRE(grid < ((int64_t)1 << 31), "dvis_x3_tile_linear_qkv: too many tiles");
-  static DvisLdsOptIn op;
-  if (const int rc = dvis_lds_opt_in((const void *)x3_tile_kernel<false, true>, k2Lds, &op, "x3_tile_kernel")) return rc;
-  hipLaunchKernelGGL((x3_tile_kernel<false, true>), dim3((unsigned)grid), dim3(256), k2Lds, (hipStream_t)stream, a);
-  return dvis_check_launch("x3_tile_kernel (qkv pack)");
+  return tile_launch<x3_tile_kernel<false, true>>(k2Lds, "x3_tile_kernel", "x3_tile_kernel (qkv pack)", a, stream);
 }
 
 DVIS_EXPORT int dvis_x3_tile_linear(const float *x, int64_t ldx, int64_t M, int K, const void *wp, int N, int xexp, int wexp,
@@ -666,22 +664,9 @@ DVIS_EXPORT int dvis_x3_tile_linear(const float *x, int64_t ldx, int64_t M, int 
   DVIS_REQUIRE(res == nullptr || ldres >= N, "dvis_x3_tile_linear: residual row stride < N");
   if (M == 0) return DVIS_OK;
   TileArgs a = {};
-  a.x = x, a.ldx = ldx, a.M = M, a.K = K, a.N = N, a.wp = (const char *)wp;
-  a.xscale = ldexpf(1.f, xexp), a.inv = ldexpf(1.f, -(xexp + wexp));
-  a.bias = bias, a.radd = res, a.ldres = ldres, a.out = out, a.ldo = ldo, a.act = act;
-  const X3Guard gd = dvis_x3_guard();
-  a.flag = gd.flag, a.tag = gd.tag;
-  const int64_t tm = (M + k2TM - 1) / k2TM;
-  a.tm = (int)tm, a.tn = N / kTN;
-  const int64_t grid = (tm + 7) / 8 * 8 * a.tn;
-  DVIS_REQUIRE(grid < ((int64_t)1 << 31), "dvis_x3_tile_linear: too many tiles");
-  static DvisLdsOptIn o2, o2g;
-  if (act == 2) {
-    if (const int rc = dvis_lds_opt_in((const void *)x3_tile_kernel<true>, k2Lds, &o2g, "x3_tile_kernel")) return rc;
-    hipLaunchKernelGGL(x3_tile_kernel<true>, dim3((unsigned)grid), dim3(256), k2Lds, (hipStream_t)stream, a);
-  } else {
-    if (const int rc = dvis_lds_opt_in((const void *)x3_tile_kernel<false>, k2Lds, &o2, "x3_tile_kernel")) return rc;
-    hipLaunchKernelGGL(x3_tile_kernel<false>, dim3((unsigned)grid), dim3(256), k2Lds, (hipStream_t)stream, a);
-  }
-  return dvis_check_launch("x3_tile_kernel");
+  if (const int rc = tile_args(a, "dvis_x3_tile_linear", x, M, K, wp, N, xexp, wexp, bias)) return rc;
+  a.x = x, a.ldx = ldx;
+  a.radd = res, a.ldres = ldres, a.out = out, a.ldo = ldo, a.act = act;
+  return act == 2 ? tile_launch<x3_tile_kernel<true>>(k2Lds, "x3_tile_kernel", "x3_tile_kernel", a, stream)
+                  : tile_launch<x3_tile_kernel<false>>(k2Lds, "x3_tile_kernel", "x3_tile_kernel", a, stream);
 }

@@ -2052,47 +2052,38 @@ def layer_norm_rows_image(x, norm, xexp=None):
 
 
 def x3_tile_linear(x, weight, bias, act=None, residual=None, xexp=None):
-    """``act(x @ weight.T + bias) + residual`` through dvis_x3_tile_linear (act: None | "relu" | "gelu")."""
+    """``act(x @ weight.T + bias) + residual`` (act: None | "relu" | "gelu") through dvis_x3_tile_linear, or for x a RowImage
+    through dvis_x3_tile_linear_image: act None / "relu" -> fp32 rows (+ residual); act "gelu" -> the next GEMM's RowImage."""
     N, K = weight.shape
-    if isinstance(x, RowImage):
-        return _x3_tile_linear_image(x, weight, bias, act, residual)
-    x2, ldx = _x3_rows(x, "x")
-    buf, wexp = x3_tile_pack(weight)
-    out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
-    rptr, ldr = _x3_residual("x3_tile_linear", residual, out)
+    image_in = isinstance(x, RowImage)
+    image_out = image_in and act == "gelu"
+    # the row operand: (image, rows) or (fp32 rows, row stride, rows); its exponent; the k order its weights are packed in
+    if image_in:
+        if x.shape[-1] != K:
+            raise RuntimeError(f"x3_tile_linear: image of {x.shape} rows against a weight of {tuple(weight.shape)}")
+        entry = "dvis_x3_tile_linear_image"
+        xargs, x_exp, order = (ctypes.c_void_p(x.data.data_ptr()), x.rows), x.exp, x.order
+    else:
+        x2, ldx = _x3_rows(x, "x")
+        entry = "dvis_x3_tile_linear"
+        xargs, x_exp, order = (ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0]), X3_XEXP if xexp is None else xexp, 0
+    buf, wexp = x3_tile_pack(weight, order)
+    # the output: (residual, its stride, fp32 rows, their stride), and for the image entry (row image, its exponent) behind them
+    no_rows, no_image = (None, 0, None, 0), (None, 0)
+    if image_out:
+        if residual is not None:
+            raise RuntimeError("x3_tile_linear: the GELU form of a row image writes a row image (no residual)")
+        out = _rows_image_buffer(x.rows, N, x.device)
+        oargs = (*no_rows, ctypes.c_void_p(out.data_ptr()), X3_XEXP)
+    else:
+        out = torch.empty((*x.shape[:-1], N), dtype=torch.float32, device=x.device)
+        rows_out = (*_x3_residual("x3_tile_linear", residual, out), ctypes.c_void_p(out.data_ptr()), N)
+        oargs = (*rows_out, *no_image) if image_in else rows_out
     with torch.cuda.device(x.device):
-        native.check(native.lib().dvis_x3_tile_linear(
-            ctypes.c_void_p(x2.data_ptr()), ldx, x2.shape[0], K, ctypes.c_void_p(buf.data_ptr()), N,
-            X3_XEXP if xexp is None else xexp, wexp, None if bias is None else native.dev_ptr(bias.detach(), "bias"),
-            {None: 0, "relu": 1, "gelu": 2}[act], rptr, ldr, ctypes.c_void_p(out.data_ptr()), N, native.stream_ptr(x.device)),
-            "dvis_x3_tile_linear")
-    return out
-
-
-def _x3_tile_linear_image(img, weight, bias, act, residual):
-    """x3_tile_linear on a RowImage.  act None / "relu": fp32 rows (+ residual); act "gelu": the result as the next GEMM's RowImage."""
-    N, K = weight.shape
-    if img.shape[-1] != K:
-        raise RuntimeError(f"x3_tile_linear: image of {img.shape} rows against a weight of {tuple(weight.shape)}")
-    M = img.rows
-    buf, wexp = x3_tile_pack(weight, img.order)
-    bptr = None if bias is None else native.dev_ptr(bias.detach(), "bias")
-    lib = native.lib()
-    with torch.cuda.device(img.device):
-        if act == "gelu":
-            if residual is not None:
-                raise RuntimeError("x3_tile_linear: the GELU form of a row image writes a row image (no residual)")
-            out = _rows_image_buffer(M, N, img.device)
-            native.check(lib.dvis_x3_tile_linear_image(ctypes.c_void_p(img.data.data_ptr()), M, K, ctypes.c_void_p(buf.data_ptr()), N, img.exp, wexp,
-                                                       bptr, 2, None, 0, None, 0, ctypes.c_void_p(out.data_ptr()), X3_XEXP,
-                                                       native.stream_ptr(img.device)), "dvis_x3_tile_linear_image")
-            return RowImage(out, (*img.shape[:-1], N), X3_XEXP, 1)
-        out = torch.empty((*img.shape[:-1], N), dtype=torch.float32, device=img.device)
-        rptr, ldr = _x3_residual("x3_tile_linear", residual, out)
-        native.check(lib.dvis_x3_tile_linear_image(ctypes.c_void_p(img.data.data_ptr()), M, K, ctypes.c_void_p(buf.data_ptr()), N, img.exp, wexp,
-                                                   bptr, {None: 0, "relu": 1}[act], rptr, ldr, ctypes.c_void_p(out.data_ptr()), N, None, 0,
-                                                   native.stream_ptr(img.device)), "dvis_x3_tile_linear_image")
-    return out
+        native.check(getattr(native.lib(), entry)(
+            *xargs, K, ctypes.c_void_p(buf.data_ptr()), N, x_exp, wexp, None if bias is None else native.dev_ptr(bias.detach(), "bias"),
+            {None: 0, "relu": 1, "gelu": 2}[act], *oargs, native.stream_ptr(x.device)), entry)
+    return RowImage(out, (*x.shape[:-1], N), X3_XEXP, 1) if image_out else out
 
 
 X3_QKV_FUSED = os.environ.get("DVIS_X3_QKV_FUSED", "1") != "0"
@@ -2101,18 +2092,15 @@ X3_QKV_FUSED = os.environ.get("DVIS_X3_QKV_FUSED", "1") != "0"
 def x3_qkv_attention_ok(x, weight, heads):
     """Can ``self_attention(x @ weight.T + bias)`` take the fused form (dvis_x3_tile_linear_qkv + dvis_attention_x3_packed)?
     x (B, L, C) float32 GPU inference tensor, weight (3C, C), head dim 64, L >= 1024 (the ViT blocks)."""
-    if isinstance(x, RowImage):
-        if len(x.shape) != 3 or not (X3_QKV_FUSED and weight.dim() == 2 and weight._base is None):
-            return False
-        B, L, C = x.shape
-        return (C == heads * 64 and weight.shape == (3 * C, C) and L >= 1024 and C >= X3_TILE_MIN_K
-                and bool(native.lib().dvis_x3_tile_supported(3 * C, C)))
-    if not (X3_QKV_FUSED and x.dim() == 3 and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and not torch.is_autocast_enabled() and x3_on() and weight.dim() == 2 and weight._base is None):
+    if len(x.shape) != 3 or not (X3_QKV_FUSED and weight.dim() == 2 and weight._base is None):
+        return False
+    if not isinstance(x, RowImage) and not (
+            x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled() and not torch.is_autocast_enabled() and x3_on()
+            and x.is_contiguous() and x.data_ptr() % 16 == 0):
         return False
     B, L, C = x.shape
-    return (C == heads * 64 and weight.shape == (3 * C, C) and L >= 1024 and x.is_contiguous() and x.data_ptr() % 16 == 0
-            and x3_tile_ok(x, 3 * C, C))
+    return (C == heads * 64 and weight.shape == (3 * C, C) and L >= 1024 and C >= X3_TILE_MIN_K
+            and bool(native.lib().dvis_x3_tile_supported(3 * C, C)))
 
 
 def x3_qkv_attention(x, weight, bias, heads, out_image=False):

@@ -431,3 +431,28 @@ def test_tiled_kernel_layout_is_exact_on_integer_operands_and_strided_rows(K, N,
     res = torch.randint(-8, 9, (M, N), generator=g).float().to(DEV)
     out = Fn.x3_tile_linear(x, w, b, act="relu", residual=res)
     assert torch.equal(out, torch.relu(ref) + res)
+
+
+@pytest.mark.parametrize("M", [1, 128, 129])
+@pytest.mark.parametrize("K", [32, 64, 96, 160])
+def test_tiled_kernel_pipeline_edges_are_exact_on_integer_operands(K, M):
+    """csrc/gemm_x3_tile.hip, x3_tile_kernel at the edges of its two-stage pipeline: K / 16 = 2 k-tiles (the prologue alone, no
+    request from the steady state), 4 (the first steady step), 6 and 10 (the register sets and LDS stages alternating more than
+    once); a lone row, an exact row tile and one row into the second tile (the clamped row address, the guarded stores); one
+    and two N-tiles (the weight stream's n-tile index).  x3_tile_ok keeps K < 512 on the streaming kernel, so the op is called
+    directly.  Integer operands: bit for bit; GELU: the tolerance of test_linear_with_gelu_and_residual_in_the_epilogue."""
+    from dvis_plus_amd import functions as Fn
+    for N in (256, 512):
+        g = torch.Generator().manual_seed(1000 * K + 10 * M + N)
+        w = torch.randint(-8, 9, (N, K), generator=g).float().to(DEV)
+        b = torch.randint(-8, 9, (N,), generator=g).float().to(DEV)
+        x = torch.randint(-8, 9, (M, K), generator=g).float().to(DEV)
+        res = torch.randint(-8, 9, (M, N), generator=g).float().to(DEV)
+        ref = x.double() @ w.double().t() + b.double()
+        assert torch.equal(Fn.x3_tile_linear(x, w, b), ref.float()), N
+        assert torch.equal(Fn.x3_tile_linear(x, w, b, act="relu", residual=res), (torch.relu(ref) + res.double()).float()), N
+        scale = x.double().abs() @ w.double().abs().t() + 1.0
+        e_f32 = _rel(F.gelu(F.linear(x, w, b)), F.gelu(ref), scale)
+        e_x3 = _rel(Fn.x3_tile_linear(x, w, b, act="gelu"), F.gelu(ref), scale)
+        assert e_x3 <= max(1.5 * e_f32, 2e-7), (N, e_x3, e_f32)
+        Fn.X3_GUARD.check_now(torch.device(DEV))

@@ -78,6 +78,34 @@ def test_rows_image_and_its_consumer_are_exact_on_integers(M, K, N):
     assert torch.equal(got[lo:lo + 50], Fn.x3_tile_linear(Fn.x3_rows_image(xf[lo:lo + 50].contiguous()), wf, None))
 
 
+@pytest.mark.parametrize("M", [1, 128, 129])
+@pytest.mark.parametrize("K", [32, 64, 96, 160])
+def test_row_image_forms_at_the_pipeline_edges(K, M):
+    """x3_tile_img_kernel at the edges of its ring of three stages: K / 16 = 2 k-tiles (the two prologue requests, none from the
+    loop), 4 (the first request from the loop), 6 (one full turn of the ring), 10 (the ring wrapping more than once); a lone
+    row, an exact row tile, one row into the second tile; one and two N-tiles.  Fn.x3_tile_linear is called directly (x3_tile_ok
+    refuses K < 512).  fp32 rows out on integers: bit for bit; the GELU -> row image form: the tolerance of
+    test_gelu_form_writes_the_next_row_image."""
+    from dvis_plus_amd import functions as Fn
+    for N in (256, 512):
+        g = torch.Generator().manual_seed(1000 * K + 10 * M + N)
+        x = _ints((M, K), -4, 5, g)                                            # dense: every k-tile counts in every output,
+        w = _ints((N, K), -4, 5, g)                                            # |hidden| stays far below the image's 4095
+        b = _ints((N,), -20, 20, g)
+        r = _ints((M, N), -30, 30, g)
+        img = Fn.x3_rows_image(x)
+        want = x.double() @ w.double().T + b.double()
+        assert torch.equal(Fn.x3_tile_linear(img, w, b), want.float()), N
+        assert torch.equal(Fn.x3_tile_linear(img, w, b, residual=r), (want + r.double()).float()), N
+        assert torch.equal(Fn.x3_tile_linear(img, w, b, act="relu", residual=r), (want.clamp_min(0) + r.double()).float()), N
+        hid = Fn.x3_tile_linear(img, w, b, act="gelu")
+        assert isinstance(hid, Fn.RowImage) and hid.order == 1 and hid.shape == (M, N)
+        gelu = Fn.x3_tile_linear(x, w, b, act="gelu")                          # fp32 rows through the same products
+        rows, _ = decode(hid)
+        assert float((rows - gelu).abs().max()) <= 2.0 ** -21 * float(gelu.abs().max()), N
+        Fn.X3_GUARD.check_now(torch.device(DEV))
+
+
 @pytest.mark.parametrize("M,C", [(300, 1024), (131, 768), (64, 512)])
 def test_layer_norm_writes_the_image_of_its_own_output(M, C):
     from dvis_plus_amd import functions as Fn
